@@ -86,8 +86,9 @@ def pmc_traffic(task, envs, aircraft, hierarchical=False):
     return best["traffic_bytes_per_launch"] if best else None
 
 
-def host_leg(env, pool, steps, warmup, sync_all=None):
-    """VecEnv.step(numpy) at the Python boundary: `warmup` untimed steps, then EXACTLY `steps` timed ones."""
+def host_leg(env, pool, steps, warmup, sync_all=None, on_last=None):
+    """VecEnv.step(numpy) at the Python boundary: `warmup` untimed steps, then EXACTLY `steps` timed ones. `on_last`, when given, is
+    called with what the last timed step returned, after the clock has stopped."""
     n = len(pool)
     for i in range(warmup):
         env.step(pool[i % n])
@@ -98,6 +99,8 @@ def host_leg(env, pool, steps, warmup, sync_all=None):
     for i in range(steps):
         res = env.step(pool[(warmup + i) % n])     # (kept in a name like a rollout loop does: step t's arrays are alive while step t + 1 runs)
     t1 = time.perf_counter()
+    if on_last is not None and res is not None:
+        on_last(res)
     del res
     if sync_all:
         sync_all()
@@ -337,6 +340,44 @@ class StubVecEnv:
         self.closed = True
 
 
+DUMP_BYTES_MAX = 64 * 10 ** 6       # --dump-outputs: files included (.npy headers counted at NPY_HEADER_BYTES each)
+NPY_HEADER_BYTES = 1024
+
+
+def info_columns(np, codes):
+    """The info words of a step as float64 columns (current_step, done code, heading_turn_counts, env-reset flag): the packed int32 words
+    of the host path (AC_INFO_* in include/aircombat.h) or the [E, 4] int32 rows of the device buffers."""
+    codes = np.asarray(codes)
+    if codes.ndim == 1:
+        w = codes.astype(np.int64) & 0xFFFFFFFF
+        return np.stack([w & 0xFFFF, (w >> 16) & 0xFF, (w >> 24) & 0x7F, (w >> 31) & 1], axis=-1).astype(np.float64)
+    return codes[:, :4].astype(np.float64)
+
+
+def step_outputs(np, res):
+    """What one VecEnv.step handed its caller, as float arrays: obs (+ share_obs for the shared-observation envs), rewards, dones, infos."""
+    names = ("obs", "share_obs", "rewards", "dones") if len(res) == 5 else ("obs", "rewards", "dones")
+    out = {k: np.array(a, dtype=np.float32) for k, a in zip(names, res[:-1])}
+    out["infos"] = info_columns(np, res[-1]._codes)
+    return out
+
+
+def dump_outputs(np, arrays, out_dir):
+    """--dump-outputs: every array as out_dir/<name>.npy. Over DUMP_BYTES_MAX in all, the same fixed, seeded sample of env rows (axis 0)
+    is kept of every array and its indices are written as sample_env_index.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    budget = DUMP_BYTES_MAX - NPY_HEADER_BYTES * (len(arrays) + 1)
+    if total > budget:
+        E = next(iter(arrays.values())).shape[0]
+        keep = max(1, int(E * (budget - 8 * E) / total))
+        idx = np.sort(np.random.default_rng(0).choice(E, size=keep, replace=False))
+        arrays = {k: a[idx] for k, a in arrays.items()}
+        arrays["sample_env_index"] = idx.astype(np.float64)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), np.ascontiguousarray(a))
+
+
 def build_config(pkg, args):
     if args.task == "heading":
         return pkg.default_config("heading")
@@ -367,7 +408,12 @@ def main():
                          "byte count in the step kernel's access pattern, used to calibrate FETCH_SIZE under rocprofv3 --pmc)")
     ap.add_argument("--host-only", action="store_true", help="profiling runs: the host-boundary leg alone (no device-resident leg, no further legs)")
     ap.add_argument("--device-only", action="store_true", help="profiling runs: skip the host-boundary leg (value = device-resident rate)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step computed (obs, rewards, dones, infos; float32 / float64) "
+                         "as DIR/<name>.npy, at most 64 MB (10^6 B) in all (rank 0)")
     args = ap.parse_args()
+    if args.dump_outputs and args.stub_env:
+        raise SystemExit("--dump-outputs needs a real env, not --stub-env")
 
     import numpy as np
     import aircombat_selfplay_amd as pkg     # (ctypes structs and host code only: neither torch nor the HIP library is loaded by the import)
@@ -435,12 +481,16 @@ def main():
 
     # ---- headline: VecEnv.step(numpy) at the Python boundary; W untimed, then exactly K timed steps between barriers
     kernel_ms = dev_wall = None
+    dumped = {}
+    keep_last = (lambda res: dumped.update(step_outputs(np, res))) if args.dump_outputs and rank == 0 else None
     if not args.device_only:
-        elapsed = host_leg(env, pool, args.steps, args.warmup, sync_all)
+        elapsed = host_leg(env, pool, args.steps, args.warmup, sync_all, on_last=keep_last)
     if args.host_only:   # profiling runs: every launch of the process is a host-boundary launch
         print(json.dumps({"metric": "agent-steps/sec", "value": float(world) * E * A * args.steps / elapsed, "unit": "agent-steps/s",
                           "ms_per_step": elapsed / args.steps * 1e3, "steps": args.steps, "warmup": args.warmup,
                           "config": {"task": args.task, "envs_per_gpu": E, "boundary": "VecEnv.step(numpy) (--host-only: no other leg)"}}))
+        if keep_last is not None:
+            dump_outputs(np, dumped, args.dump_outputs)
         env.close()
         if dist is not None:
             dist.destroy_process_group()
@@ -453,6 +503,10 @@ def main():
         sync_all()
         if args.device_only:
             elapsed = dev_wall
+            if keep_last is not None:     # the timed path wrote its outputs to HBM: the device buffers as the caller of step_device sees them
+                _, d_obs, d_rew, d_done, d_info = env.device_tensors()
+                dumped.update(obs=d_obs.cpu().numpy().astype(np.float32), rewards=d_rew.cpu().numpy().astype(np.float32),
+                              dones=d_done.cpu().numpy().astype(np.float32), infos=info_columns(np, d_info.cpu().numpy()))
     red = pkg.sharding.max_over_ranks([elapsed, dev_wall or 0.0, kernel_ms or 0.0], dist, device=red_dev)
     elapsed, dev_wall, kernel_ms = red
     # who took part: one SUM all-reduce on the job's group (RCCL for N > 1 on GPUs) with every rank's device ordinal, PCI bus id and work
@@ -595,6 +649,8 @@ def main():
     if dist is not None:
         dist.destroy_process_group()
     if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(np, dumped, args.dump_outputs)
         print(json.dumps(result))
 
 
