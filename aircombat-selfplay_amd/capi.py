@@ -13,6 +13,7 @@ AC_STATE_LEN = 128
 AC_TASK_HEADING, AC_TASK_SINGLECOMBAT, AC_TASK_DODGE_MISSILE, AC_TASK_SHOOT_MISSILE, AC_TASK_MULTICOMBAT = 0, 1, 2, 3, 4
 AC_TASK_SCENARIO1, AC_TASK_SCENARIO_NVN, AC_TASK_WVR, AC_TASK_MANEUVER = 5, 6, 7, 8
 AC_ALIVE, AC_CRASH, AC_SHOTDOWN = 0, 1, 2
+AC_CTL_FAST, AC_CTL_FP32 = 0, 1   # AcConfig.controller_precision: the low-level controller's arithmetic
 
 
 class HipExtensionMissing(RuntimeError):
@@ -68,6 +69,7 @@ class AcConfig(C.Structure):
         ("rwr", C.c_int32),
         ("use_baseline", C.c_int32),
         ("hierarchical", C.c_int32), ("approach", C.c_int32),
+        ("controller_precision", C.c_int32),
     ]
 
 
@@ -111,6 +113,9 @@ SIGNATURES = {
     "ac_unpin_host_buffer": (C.c_int, [_p, _p]),
     "ac_load_controller": (C.c_int, [_p, _p, C.c_int64]),
     "ac_split_f16x2": (C.c_int, [_p, C.c_int64, _p, _p]),
+    "ac_split_bf16x3": (C.c_int, [_p, C.c_int64, _p, _p, _p]),
+    "ac_controller_precision": (C.c_int, [_p]),
+    "ac_controller_forward": (C.c_int, [C.c_int32, C.c_int32, _p, C.c_int64, C.c_int64, _p, _p, _p, _p]),
     "ac_selftest_missile_walk": (C.c_int, [C.c_int32, _p]),
     "ac_get_controller_state": (C.c_int, [_p, C.c_int32, C.c_int32, _p, _p]),
     "ac_set_controller_state": (C.c_int, [_p, C.c_int32, C.c_int32, _p]),

@@ -1703,7 +1703,8 @@ struct ac_env {
   float* d_XF; int* d_XI;                // scenario-task extension state
   double* d_state_io;                    // ac_get_state / ac_set_state: one aircraft's record on its way through (state_io_kernel)
   float* d_low;                          // hierarchical tasks: low-level action buffer (the controller's output, the step kernel's input)
-  float* d_ctlWs8;                       // controller weights as fp16 pieces in the kernel's tiling (controller8_kernel.hpp)
+  float* d_ctlWs8;                       // controller weights as 16-bit pieces in the kernel's tiling (controller8_kernel.hpp)
+  int ctl_np;                            // pieces per controller value: 2 (AC_CTL_FAST) or 3 (AC_CTL_FP32; cfg or AIRCOMBAT_CTL_PRECISION)
   int ctl_rows;                          // aircraft per controller workgroup pinned by AIRCOMBAT_CTL_ROWS=32/64 (0: chosen per grid)
   HeadingPtrs hp; HeadingCfg hc;         // HeadingTask: targets, check clock, numpy-PCG64 state per env
   int act_low;                           // width of the low-level action the step kernels decode
@@ -1741,6 +1742,13 @@ static int check_nonfinite(ac_env* h, const char* who) {
   snprintf(msg, sizeof msg, "%s: JSBSim failed. Non-finite state or reward in env %d, agent %d (ac_reset clears the condition)", who, n / h->A, n % h->A);
   return fail(msg);
 }
+// aircraft per controller workgroup: 32 while that leaves no CU with two tiles to do one after the other, 64 beyond; `pinned`
+// (AIRCOMBAT_CTL_ROWS) overrides it
+static int ctl_rows_for(int N, int pinned) { return pinned ? pinned : ((N + 31) / 32 > 256 ? 64 : 32); }
+static int ctl_rows_pin() {
+  const char* cr = getenv("AIRCOMBAT_CTL_ROWS");
+  return cr ? (atoi(cr) == 64 ? 64 : 32) : 0;
+}
 static int launch_step(ac_env* h, const float* d_actions, int host_set = -1) {
   DevPtrs p = h->dp;
   p.actions = d_actions ? d_actions : h->d_actions;
@@ -1757,9 +1765,15 @@ static int launch_step(ac_env* h, const float* d_actions, int host_set = -1) {
     // (the scripted opponents' inputs -- use_baseline -- are computed inside that instantiation of the kernel)
     {   // eight waves per tile (controller8_kernel.hpp): 32 aircraft per workgroup while that leaves no CU with two tiles to do one
         // after the other, 64 beyond (AIRCOMBAT_CTL_ROWS pins it for tests)
-      const int rows = h->ctl_rows ? h->ctl_rows : ((h->N + 31) / 32 > 256 ? 64 : 32);
+      const int rows = ctl_rows_for(h->N, h->ctl_rows);
       const dim3 g8((h->N + rows - 1) / rows);
-      if (rows == 64) {
+      if (h->ctl_np == 3) {   // the reference-precision form (three bf16 pieces)
+        if (rows == 64) {
+          if (h->cfg.use_baseline) hipLaunchKernelGGL((controller8x3_kernel<true, 4>), g8, dim3(512), 0, h->stream, a);
+          else hipLaunchKernelGGL((controller8x3_kernel<false, 4>), g8, dim3(512), 0, h->stream, a);
+        } else if (h->cfg.use_baseline) hipLaunchKernelGGL((controller8x3_kernel<true, 2>), g8, dim3(512), 0, h->stream, a);
+        else hipLaunchKernelGGL((controller8x3_kernel<false, 2>), g8, dim3(512), 0, h->stream, a);
+      } else if (rows == 64) {
         if (h->cfg.use_baseline) hipLaunchKernelGGL((controller8_kernel<true, 4>), g8, dim3(512), 0, h->stream, a);
         else hipLaunchKernelGGL((controller8_kernel<false, 4>), g8, dim3(512), 0, h->stream, a);
       } else if (h->cfg.use_baseline) hipLaunchKernelGGL((controller8_kernel<true, 2>), g8, dim3(512), 0, h->stream, a);
@@ -1881,6 +1895,16 @@ int ac_create(const ac_config_t* cfg, int32_t n_envs, int32_t device_id, uint64_
     if ((cfg->n_agents != 4 && cfg->n_agents != 8) || cfg->n_ego <= 0 || cfg->n_ego >= cfg->n_agents)
       return fail("ac_create: AC_TASK_MULTICOMBAT needs n_agents in {4, 8} and 0 < n_ego < n_agents");
   } else if (!heading && (cfg->n_agents != 2 || cfg->n_ego != 1)) return fail("ac_create: 1v1 tasks need n_agents == 2 and n_ego == 1");
+  if (cfg->controller_precision != AC_CTL_FAST && cfg->controller_precision != AC_CTL_FP32)
+    return fail("ac_create: unknown controller_precision (AC_CTL_FAST = 0, AC_CTL_FP32 = 1)");
+  if (cfg->controller_precision != AC_CTL_FAST && !cfg->hierarchical)
+    return fail("ac_create: controller_precision selects the form of the low-level controller; it needs cfg.hierarchical");
+  int ctl_prec = cfg->controller_precision;
+  if (const char* pe = getenv("AIRCOMBAT_CTL_PRECISION")) {   // pins the form of every hierarchical handle (tests)
+    if (!strcmp(pe, "fast")) ctl_prec = AC_CTL_FAST;
+    else if (!strcmp(pe, "fp32")) ctl_prec = AC_CTL_FP32;
+    else return fail("ac_create: AIRCOMBAT_CTL_PRECISION must be 'fast' or 'fp32'");
+  }
   if (cfg->use_baseline && (!cfg->hierarchical || cfg->use_baseline < 0 || cfg->use_baseline > 2 || cfg->n_ego * 2 != cfg->n_agents))
     return fail("ac_create: use_baseline (1 pursue, 2 maneuver) needs the hierarchical form and equal teams (enemy k is flown by scripted agent k)");
   if ((cfg->task == AC_TASK_WVR || cfg->task == AC_TASK_MANEUVER) && (cfg->n_agents != 2 || cfg->n_ego != 1 || cfg->rwr))
@@ -1903,6 +1927,8 @@ int ac_create(const ac_config_t* cfg, int32_t n_envs, int32_t device_id, uint64_
   ac_env* h = new ac_env();
   memset(h, 0, sizeof *h);
   h->cfg = *cfg; h->E = n_envs; h->A = cfg->n_agents; h->N = n_envs * cfg->n_agents; h->device = device_id;
+  h->cfg.controller_precision = cfg->hierarchical ? ctl_prec : AC_CTL_FAST;
+  h->ctl_np = h->cfg.controller_precision == AC_CTL_FP32 ? 3 : 2;
   {  // Kernel form. Tasks whose substeps are the FDM tick alone: three waves per 64 aircraft (split_kernel.hpp) while the chip has
      // SIMDs to spare -- up to 512 workgroups (1536 waves on 256 CUs x 4 SIMDs; measured faster than one wave per 64 aircraft up to
      // there, slower from 768 on); AIRCOMBAT_SPLIT=0/1 overrides that choice. Tasks with munitions always run the pair form
@@ -1912,8 +1938,7 @@ int ac_create(const ac_config_t* cfg, int32_t n_envs, int32_t device_id, uint64_
     const bool ticks_only = cfg->task == AC_TASK_SINGLECOMBAT || cfg->task == AC_TASK_MULTICOMBAT || cfg->task == AC_TASK_HEADING ||
                             cfg->task == AC_TASK_WVR || cfg->task == AC_TASK_MANEUVER;
     h->split_waves = ticks_only && (e ? (e[0] == '1') : (wgs <= 512));
-    const char* cr = getenv("AIRCOMBAT_CTL_ROWS");
-    h->ctl_rows = cr ? (atoi(cr) == 64 ? 64 : 32) : 0;
+    h->ctl_rows = ctl_rows_pin();
     const char* qe = getenv("AIRCOMBAT_QUAD");   // 0 / 1 overrides the choice of the quad form
     const bool munitions_1v1 = cfg->task == AC_TASK_SHOOT_MISSILE || (cfg->task == AC_TASK_DODGE_MISSILE && !nvn_dodge) || cfg->task == AC_TASK_SCENARIO1;
     h->quad_waves = munitions_1v1 && (qe ? (qe[0] == '1') : (wgs <= 256));
@@ -2448,39 +2473,113 @@ int ac_unpin_host_buffer(ac_env_t* h, void* ptr) {
   HIP_OK(hipHostUnregister(ptr));
   return 0;
 }
-int ac_load_controller(ac_env_t* h, const float* weights, int64_t n) {
+}  // extern "C"
+
+// The controller weights (the 137753 floats of tools/export_baseline_actor.py) as NP 16-bit pieces in the kernel's tiling: tile(c) = the 16
+// columns 16 c .. 16 c + 15 = K/32 k-steps x NP pieces x 64 lanes x 8 values, element (s, p, lane, i) = piece p of W[j = 16 c + lane % 16]
+// [k = 32 s + 8 (lane / 16) + i]; the biases and LayerNorm scales / shifts behind them in fp32 (controller8_kernel.hpp, Lay<NP>).
+template <int NP>
+static std::vector<float> controller_blob(const float* weights) {
   using namespace ctl;
+  using L = ctl8::Lay<NP>;
+  std::vector<float> e(L::C_END, 0.0f);
+  unsigned short* e16 = reinterpret_cast<unsigned short*>(e.data());
+  auto tiles_s = [&](int src, int dst, int J, int K, int Kpad, int ntiles) {
+    for (int c = 0; c < ntiles; ++c)
+      for (int st = 0; st < Kpad / 32; ++st)
+        for (int lane = 0; lane < 64; ++lane)
+          for (int i = 0; i < 8; ++i) {
+            const int k = 32 * st + 8 * (lane / 16) + i, j = 16 * c + lane % 16;
+            const float v = (j < J && k < K) ? weights[src + j * K + k] : 0.0f;
+            unsigned pc[3];
+            if (NP == 2) ctls::split2(v, pc[0], pc[1]);
+            else ctls::split3(v, pc[0], pc[1], pc[2]);
+            for (int pp = 0; pp < NP; ++pp)
+              e16[(size_t)dst * 2 + ((((size_t)c * (Kpad / 32) + st) * NP + pp) * 64 + lane) * 8 + i] = (unsigned short)pc[pp];
+          }
+  };
+  auto copy_s = [&](int src, int dst, int cnt) { for (int i = 0; i < cnt; ++i) e[dst + i] = weights[src + i]; };
+  tiles_s(S_W1, L::C_W1, 128, 12, 32, 8); copy_s(S_B1, L::C_B1, 128); copy_s(S_G1, L::C_G1, 128); copy_s(S_BE1, L::C_BE1, 128);
+  tiles_s(S_W2, L::C_W2, 128, 128, 128, 8); copy_s(S_B2, L::C_B2, 128); copy_s(S_G2, L::C_G2, 128); copy_s(S_BE2, L::C_BE2, 128);
+  // (W_ih / W_hh rows are gate-major: r 0..127, z 128..255, n 256..383, so tile 8 g + u is columns 128 g + 16 u .. + 15 = tile index c of the stacked matrix)
+  tiles_s(S_WIH, L::C_WIH, 384, 128, 128, 24); tiles_s(S_WHH, L::C_WHH, 384, 128, 128, 24); copy_s(S_BIH, L::C_BIH, 384); copy_s(S_BHH, L::C_BHH, 384);
+  copy_s(S_G3, L::C_G3, 128); copy_s(S_BE3, L::C_BE3, 128);
+  tiles_s(S_WA, L::C_WA, NH, 128, 128, 10); copy_s(S_BA, L::C_BA, NH);
+  return e;
+}
+// the checks both loaders share; the reference-precision form refuses non-finite weights (bf16 pieces have fp32's range: nothing else to check)
+static int controller_weights_ok(const char* who, int np, const float* weights, int64_t n) {
+  if (n != ctl::S_END) return fail(std::string(who) + ": expected 137753 floats (layout of tools/export_baseline_actor.py)");
+  if (np == 3)
+    for (int64_t i = 0; i < n; ++i)
+      if (!std::isfinite(weights[i]))
+        return fail(std::string(who) + ": non-finite controller weight at index " + std::to_string(i) + " (the fp32 form takes finite weights only)");
+  return 0;
+}
+
+extern "C" {
+int ac_load_controller(ac_env_t* h, const float* weights, int64_t n) {
   if (!h || !weights) return fail("ac_load_controller: null argument");
   if (!h->cfg.hierarchical) return fail("ac_load_controller: the handle was not created with cfg.hierarchical");
-  if (n != S_END) return fail("ac_load_controller: expected 137753 floats (layout of tools/export_baseline_actor.py)");
+  if (controller_weights_ok("ac_load_controller", h->ctl_np, weights, n)) return -1;
   HIP_OK(hipSetDevice(h->device));
-  {   // the weights as fp16 pieces in the kernel's tiling: tile(c) = the 16 columns 16 c .. 16 c + 15 = K/32 k-steps x 2 pieces x 64 lanes x 8 values,
-      // element (s, p, lane, i) = piece p of W[j = 16 c + lane % 16][k = 32 s + 8 (lane / 16) + i]
-    using namespace ctl8;
-    std::vector<float> e(C_END, 0.0f);
-    unsigned short* e16 = reinterpret_cast<unsigned short*>(e.data());
-    auto tiles_s = [&](int src, int dst, int J, int K, int Kpad, int ntiles) {
-      for (int c = 0; c < ntiles; ++c)
-        for (int st = 0; st < Kpad / 32; ++st)
-          for (int lane = 0; lane < 64; ++lane)
-            for (int i = 0; i < 8; ++i) {
-              const int k = 32 * st + 8 * (lane / 16) + i, j = 16 * c + lane % 16;
-              unsigned pc[NP];
-              ctls::split2((j < J && k < K) ? weights[src + j * K + k] : 0.0f, pc[0], pc[1]);
-              for (int pp = 0; pp < NP; ++pp)
-                e16[(size_t)dst * 2 + ((((size_t)c * (Kpad / 32) + st) * NP + pp) * 64 + lane) * 8 + i] = (unsigned short)pc[pp];
-            }
-    };
-    auto copy_s = [&](int src, int dst, int cnt) { for (int i = 0; i < cnt; ++i) e[dst + i] = weights[src + i]; };
-    tiles_s(S_W1, C_W1, 128, 12, 32, 8); copy_s(S_B1, C_B1, 128); copy_s(S_G1, C_G1, 128); copy_s(S_BE1, C_BE1, 128);
-    tiles_s(S_W2, C_W2, 128, 128, 128, 8); copy_s(S_B2, C_B2, 128); copy_s(S_G2, C_G2, 128); copy_s(S_BE2, C_BE2, 128);
-    // (W_ih / W_hh rows are gate-major: r 0..127, z 128..255, n 256..383, so tile 8 g + u is columns 128 g + 16 u .. + 15 = tile index c of the stacked matrix)
-    tiles_s(S_WIH, C_WIH, 384, 128, 128, 24); tiles_s(S_WHH, C_WHH, 384, 128, 128, 24); copy_s(S_BIH, C_BIH, 384); copy_s(S_BHH, C_BHH, 384);
-    copy_s(S_G3, C_G3, 128); copy_s(S_BE3, C_BE3, 128);
-    tiles_s(S_WA, C_WA, NH, 128, 128, 10); copy_s(S_BA, C_BA, NH);
-    if (!h->d_ctlWs8) HIP_OK(hipMalloc(&h->d_ctlWs8, sizeof(float) * C_END));
-    HIP_OK(hipMemcpy(h->d_ctlWs8, e.data(), sizeof(float) * C_END, hipMemcpyHostToDevice));
+  // laid out for the handle's form (controller8_kernel.hpp)
+  const std::vector<float> e = h->ctl_np == 3 ? controller_blob<3>(weights) : controller_blob<2>(weights);
+  if (!h->d_ctlWs8) HIP_OK(hipMalloc(&h->d_ctlWs8, sizeof(float) * e.size()));
+  HIP_OK(hipMemcpy(h->d_ctlWs8, e.data(), sizeof(float) * e.size(), hipMemcpyHostToDevice));
+  return 0;
+}
+int ac_controller_precision(ac_env_t* h) {
+  if (!h) return fail("ac_controller_precision: null handle");
+  return h->cfg.controller_precision;
+}
+int ac_controller_forward(int32_t device_id, int32_t precision, const float* weights, int64_t n_weights, int64_t n, const float* x, float* h,
+                          float* logits, int32_t* action) {
+  if (!weights || !x || !h || !action || n <= 0) return fail("ac_controller_forward: bad argument");
+  if (precision != AC_CTL_FAST && precision != AC_CTL_FP32) return fail("ac_controller_forward: unknown precision (AC_CTL_FAST = 0, AC_CTL_FP32 = 1)");
+  if (n > (1 << 23)) return fail("ac_controller_forward: more than 2^23 rows in one call");
+  const int np = precision == AC_CTL_FP32 ? 3 : 2;
+  if (controller_weights_ok("ac_controller_forward", np, weights, n_weights)) return -1;
+  int ndev = 0;
+  HIP_OK(hipGetDeviceCount(&ndev));
+  if (device_id < 0 || device_id >= ndev) return fail("ac_controller_forward: no such HIP device");
+  HIP_OK(hipSetDevice(device_id));
+  const std::vector<float> blob = np == 3 ? controller_blob<3>(weights) : controller_blob<2>(weights);
+  const size_t N = (size_t)n;
+  std::vector<float> hT(128 * N);   // the kernel's state layout is [128][N]
+  for (size_t i = 0; i < N; ++i)
+    for (int k = 0; k < 128; ++k) hT[(size_t)k * N + i] = h[i * 128 + k];
+  float *dW = nullptr, *dx = nullptr, *dH = nullptr, *dlg = nullptr, *dlow = nullptr;
+  hipError_t err = hipSuccess;
+  auto ok = [&](hipError_t e) { if (err == hipSuccess) err = e; return err == hipSuccess; };
+  std::vector<float> low(4 * N);
+  if (ok(hipMalloc(&dW, sizeof(float) * blob.size())) && ok(hipMalloc(&dx, sizeof(float) * 12 * N)) && ok(hipMalloc(&dH, sizeof(float) * 128 * N)) &&
+      ok(hipMalloc(&dlow, sizeof(float) * 4 * N)) && (!logits || ok(hipMalloc(&dlg, sizeof(float) * ctl::NH * N))) &&
+      ok(hipMemcpy(dW, blob.data(), sizeof(float) * blob.size(), hipMemcpyHostToDevice)) &&
+      ok(hipMemcpy(dx, x, sizeof(float) * 12 * N, hipMemcpyHostToDevice)) &&
+      ok(hipMemcpy(dH, hT.data(), sizeof(float) * 128 * N, hipMemcpyHostToDevice))) {
+    ctl::Args a{};
+    a.Ws8 = dW; a.H = dH; a.low = dlow; a.N = (int)n; a.act_low = 4; a.A = 1;
+    const int rows = ctl_rows_for((int)n, ctl_rows_pin());
+    const dim3 g8((unsigned)((n + rows - 1) / rows));
+    if (np == 3) {
+      if (rows == 64) hipLaunchKernelGGL((controller8_forward_kernel<3, 4>), g8, dim3(512), 0, 0, a, dx, dlg);
+      else hipLaunchKernelGGL((controller8_forward_kernel<3, 2>), g8, dim3(512), 0, 0, a, dx, dlg);
+    } else if (rows == 64) hipLaunchKernelGGL((controller8_forward_kernel<2, 4>), g8, dim3(512), 0, 0, a, dx, dlg);
+    else hipLaunchKernelGGL((controller8_forward_kernel<2, 2>), g8, dim3(512), 0, 0, a, dx, dlg);
+    if (ok(hipGetLastError()) && ok(hipDeviceSynchronize()) &&
+        ok(hipMemcpy(hT.data(), dH, sizeof(float) * 128 * N, hipMemcpyDeviceToHost)) &&
+        ok(hipMemcpy(low.data(), dlow, sizeof(float) * 4 * N, hipMemcpyDeviceToHost)) &&
+        (!logits || ok(hipMemcpy(logits, dlg, sizeof(float) * ctl::NH * N, hipMemcpyDeviceToHost)))) {
+      for (size_t i = 0; i < N; ++i) {
+        for (int k = 0; k < 128; ++k) h[i * 128 + k] = hT[(size_t)k * N + i];
+        for (int k = 0; k < 4; ++k) action[i * 4 + k] = (int32_t)low[i * 4 + k];
+      }
+    }
   }
+  for (float* p : {dW, dx, dH, dlg, dlow})
+    if (p) (void)hipFree(p);
+  if (err != hipSuccess) return fail(std::string("ac_controller_forward: ") + hipGetErrorString(err));
   return 0;
 }
 int ac_split_f16x2(const float* x, int64_t n, float* hi, float* lo) {
@@ -2490,6 +2589,16 @@ int ac_split_f16x2(const float* x, int64_t n, float* hi, float* lo) {
     ctls::split2(x[i], p[0], p[1]);
     float* out[2] = {hi, lo};
     for (int k = 0; k < 2; ++k) { const unsigned short b = (unsigned short)p[k]; _Float16 v; memcpy(&v, &b, 2); out[k][i] = (float)v; }
+  }
+  return 0;
+}
+int ac_split_bf16x3(const float* x, int64_t n, float* b0, float* b1, float* b2) {
+  if (!x || !b0 || !b1 || !b2 || n < 0) return fail("ac_split_bf16x3: bad argument");
+  for (int64_t i = 0; i < n; ++i) {
+    unsigned p[3];
+    ctls::split3(x[i], p[0], p[1], p[2]);
+    float* out[3] = {b0, b1, b2};
+    for (int k = 0; k < 3; ++k) { const uint32_t b = p[k] << 16; float v; memcpy(&v, &b, 4); out[k][i] = v; }
   }
   return 0;
 }

@@ -19,6 +19,13 @@
 //
 // Weights are split once on the host (ac_load_controller); activations are split where they are produced -- the LayerNorm epilogue writes
 // two fp16 planes [aircraft][k] to LDS, so an A operand (8 consecutive k of one aircraft) is one ds_read_b128 per piece.
+// The reference-precision form (AC_CTL_FP32, opt-in per handle) keeps that older arithmetic: three bf16 pieces, b0 = bf16(x),
+// b1 = bf16(x - b0), b2 = bf16(x - b0 - b1), each rounded to nearest-even. Both subtractions are exact and, for normal fp32 x, the pieces
+// add up to x exactly (x - b0 has at most 15 significant bits, what b1 leaves at most 8 -- a bf16 holds 8); with the build's
+// flush-to-zero that holds while the smaller pieces stay normal numbers (they are multiples of x's last place: |x| >= 2^-103) and b0 does
+// not round beyond bf16's largest finite value (|x| < 2^128 (1 - 2^-9)); below 2^-103 what is lost is under 2^-126. The six terms of a product with i + j <= 2 (b0b0, b0b1, b1b0, b0b2, b1b1, b2b0) leave out three of at most
+// 2^-24 of it: each product is good to about 2^-23 of itself, at least fp32's own rounding, on the bf16 matrix path
+// (v_mfma_f32_16x16x32_bf16: six of them per 32 k of a tile, 96 cycles, against 256 for the fp32-input instruction).
 // (History: round 1 ran the GEMMs on v_mfma_f32_32x32x2_f32 (27 us per call at 8192 aircraft); rounds 2-3 on a four-wave kernel of
 // v_mfma_f32_32x32x16_bf16 with three bf16 pieces per value and six kept terms, one wave per SIMD with 378 registers of weight prefetch
 // (20-22 us; 39 / 75 us at 16 384 / 32 768); round 4's eight-wave kernel replaced it on every grid (18.0 / 27.6 / 53.6 us), then went
@@ -48,4 +55,29 @@ __device__ __forceinline__ void split2_pair(float a, float b, unsigned& hi, unsi
   hi = __builtin_bit_cast(unsigned, h);
   lo = __builtin_bit_cast(unsigned, __builtin_convertvector(r, f16x2));
 }
+// x = b0 + b1 + b2 (bit patterns of the three bf16), round-to-nearest-even each
+__host__ __device__ __forceinline__ void split3(float x, unsigned& b0, unsigned& b1, unsigned& b2) {
+  const __bf16 p0 = (__bf16)x;
+  const float r1 = x - (float)p0;
+  const __bf16 p1 = (__bf16)r1;
+  const __bf16 p2 = (__bf16)(r1 - (float)p1);
+  unsigned short u0, u1, u2;
+  memcpy(&u0, &p0, 2); memcpy(&u1, &p1, 2); memcpy(&u2, &p2, 2);
+  b0 = u0; b1 = u1; b2 = u2;
+}
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+// two values at once on the device (v_cvt_pk_bf16_f32 rounds a pair to nearest-even and packs it)
+__device__ __forceinline__ void split3_pair(float a, float b, unsigned& b0, unsigned& b1, unsigned& b2) {
+  const floatx2 f = {a, b};
+  const bf16x2 p0 = __builtin_convertvector(f, bf16x2);
+  const floatx2 r1 = f - __builtin_convertvector(p0, floatx2);
+  const bf16x2 p1 = __builtin_convertvector(r1, bf16x2);
+  const floatx2 r2 = r1 - __builtin_convertvector(p1, floatx2);
+  b0 = __builtin_bit_cast(unsigned, p0);
+  b1 = __builtin_bit_cast(unsigned, p1);
+  b2 = __builtin_bit_cast(unsigned, __builtin_convertvector(r2, bf16x2));
+}
+// a bf16 bit pattern (low 16 bits) as the fp32 it stands for
+__device__ __forceinline__ float bf16_bits_to_f32(unsigned b) { return __uint_as_float(b << 16); }
 }  // namespace ctls

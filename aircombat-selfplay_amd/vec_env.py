@@ -24,7 +24,7 @@ import sys
 import numpy as np
 
 from .capi import (AcConfig, AC_STATE_LEN, AC_TASK_HEADING, AC_TASK_SINGLECOMBAT, AC_TASK_SHOOT_MISSILE, AC_TASK_MULTICOMBAT, AC_TASK_SCENARIO1,
-                   AC_TASK_SCENARIO_NVN, load_library)
+                   AC_TASK_SCENARIO_NVN, AC_CTL_FAST, AC_CTL_FP32, load_library)
 from .config import config_from_yaml, default_config
 
 DONE_MESSAGES = {
@@ -131,6 +131,42 @@ def _spaces():
 
 
 CONTROLLER_WEIGHTS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "data", "baseline_actor.f32")
+# the low-level controller's arithmetic (AcConfig.controller_precision, include/aircombat.h): "fast" = two fp16 pieces per value (the
+# default), "fp32" = three bf16 pieces, every product at least as exact as the reference's fp32
+CONTROLLER_PRECISIONS = {"fast": AC_CTL_FAST, "fp32": AC_CTL_FP32}
+
+
+def _controller_precision_id(name):
+    if name not in CONTROLLER_PRECISIONS:
+        raise ValueError(f"controller_precision must be one of {sorted(CONTROLLER_PRECISIONS)}, not {name!r}")
+    return CONTROLLER_PRECISIONS[name]
+
+
+def controller_forward(x, h, precision="fast", device=0, weights=None):
+    """The low-level controller (the reference's BaselineActor) on given inputs, batched on the device, no env needed.
+
+    ``x`` [n, 12] inputs and ``h`` [n, 128] GRU states (or one row of each) -> ``(action, h_new, logits)``:
+    the four argmax indices [n, 4] (int32), the new GRU state [n, 128] and the 153 stacked head logits [n, 153] (float32).
+    ``precision``: "fast" or "fp32" (see ``CONTROLLER_PRECISIONS``). ``weights``: the exported blob, default data/baseline_actor.f32."""
+    prec = _controller_precision_id(precision)
+    x = np.asarray(x, dtype=np.float32)
+    h = np.asarray(h, dtype=np.float32)
+    single = x.ndim == 1
+    x = np.ascontiguousarray(x.reshape(-1, 12))
+    h_new = np.array(h.reshape(-1, 128), dtype=np.float32, order="C")   # a copy: updated in place
+    if x.shape[0] != h_new.shape[0]:
+        raise ValueError(f"x has {x.shape[0]} rows, h {h_new.shape[0]}")
+    n = x.shape[0]
+    w = np.ascontiguousarray(np.fromfile(CONTROLLER_WEIGHTS, dtype=np.float32) if weights is None else weights, dtype=np.float32)
+    logits = np.empty((n, 153), dtype=np.float32)
+    action = np.empty((n, 4), dtype=np.int32)
+    lib = load_library()
+    lib.check(lib.ac_controller_forward(int(device), prec, w.ctypes.data, int(w.size), n, x.ctypes.data, h_new.ctypes.data,
+                                        logits.ctypes.data, action.ctypes.data), "ac_controller_forward")
+    if single:
+        return action[0], h_new[0], logits[0]
+    return action, h_new, logits
+
 
 
 RING_SETS = 4        # result sets the default mode cycles through (the library allows AC_HOST_SETS = 8; one more is the staging set)
@@ -162,9 +198,13 @@ class _Mapped:
 class HipVecEnv:
     """E parallel 1v1 air-combat envs advanced by one HIP kernel launch per ``step``."""
 
-    def __init__(self, config, num_envs, device_id=0, seed=0, lib=None, copy=True):
+    def __init__(self, config, num_envs, device_id=0, seed=0, lib=None, copy=True, controller_precision=None):
         if not isinstance(config, AcConfig):
             raise TypeError("config must be an AcConfig (see config_from_yaml / default_config)")
+        if controller_precision is not None:   # "fast" / "fp32": the low-level controller's form (None: the config's field)
+            prec = _controller_precision_id(controller_precision)
+            config = AcConfig.from_buffer_copy(config)
+            config.controller_precision = prec
         self.lib = lib or load_library()
         self.config = config
         self.copy = bool(copy)
@@ -514,6 +554,14 @@ class HipVecEnv:
         self.lib.check(self.lib.ac_get_heading_state(self._h, env, out), "ac_get_heading_state")
         return np.array(out[:])
 
+    @property
+    def controller_precision(self):
+        """The form of the low-level controller this handle runs: "fast" or "fp32" (after any AIRCOMBAT_CTL_PRECISION pin)."""
+        prec = self.lib.ac_controller_precision(self._h)
+        if prec < 0:
+            raise RuntimeError(f"ac_controller_precision failed: {self.lib.last_error()}")
+        return {AC_CTL_FAST: "fast", AC_CTL_FP32: "fp32"}[prec]
+
     def get_controller_state(self, env, agent):
         """(hidden[128], low_action[act_low]) of the low-level controller for one aircraft (hierarchical tasks)."""
         hid = np.zeros(128, dtype=np.float32)
@@ -550,8 +598,8 @@ class HipShareVecEnv(HipVecEnv):
     observations of env ``e`` (BaseEnv.get_state, env_base.py:183-189), i.e. ``obs`` flattened per env; it is returned as a
     read-only broadcast view (the buffers copy on insert)."""
 
-    def __init__(self, config, num_envs, device_id=0, seed=0, lib=None, copy=True):
-        super().__init__(config, num_envs, device_id=device_id, seed=seed, lib=lib, copy=copy)
+    def __init__(self, config, num_envs, device_id=0, seed=0, lib=None, copy=True, controller_precision=None):
+        super().__init__(config, num_envs, device_id=device_id, seed=seed, lib=lib, copy=copy, controller_precision=controller_precision)
         Box = _spaces()[0]
         self.share_observation_space = Box(low=-10, high=10.0, shape=(self.num_agents * self.obs_dim,))
 
@@ -659,8 +707,9 @@ class MultiDeviceVecEnv:
         self._pool.shutdown(wait=True)
 
 
-def make_env(scenario=None, num_envs=1, task=None, device_id=0, seed=0, copy=True):
-    """``scenario``: path of a scenario YAML (reference format) or None for the 1v1 block of WVR_selfplay.yaml."""
+def make_env(scenario=None, num_envs=1, task=None, device_id=0, seed=0, copy=True, controller_precision=None):
+    """``scenario``: path of a scenario YAML (reference format) or None for the 1v1 block of WVR_selfplay.yaml.
+    ``controller_precision``: "fast" / "fp32" for the hierarchical tasks' low-level controller (None: the default, "fast")."""
     cfg = config_from_yaml(scenario, task=task) if scenario else default_config(task or "singlecombat")
     cls = HipShareVecEnv if cfg.n_agents > 2 else HipVecEnv         # the MultipleCombatEnv family (share_obs)
-    return cls(cfg, num_envs, device_id=device_id, seed=seed, copy=copy)
+    return cls(cfg, num_envs, device_id=device_id, seed=seed, copy=copy, controller_precision=controller_precision)

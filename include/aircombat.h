@@ -91,7 +91,14 @@ typedef struct ac_config {
   int32_t approach;                 /* AC_TASK_HEADING only: ApproachTask (`task: approach`, tasks/approach_task.py:9-120): the same env, reset
                                        draws and observation, reward = AltitudeReward alone, terminations LowAltitude, ExtremeState,
                                        Overload, Timeout (no UnreachHeading: the targets stay at their reset values) */
+  int32_t controller_precision;     /* with cfg.hierarchical: the arithmetic of the low-level controller's products. AC_CTL_FAST (0, the
+                                       default): two fp16 pieces per value, three terms per product (22 bits per value, the fastest form);
+                                       AC_CTL_FP32: three bf16 pieces, six terms -- every product at least as exact as the reference's fp32
+                                       (torch on the CPU), at about 1.5x the controller's time. ac_create refuses other values, and a
+                                       non-zero value without cfg.hierarchical. AIRCOMBAT_CTL_PRECISION=fast|fp32 in the environment pins
+                                       the form of every hierarchical handle created while it is set. */
 } ac_config_t;
+enum { AC_CTL_FAST = 0, AC_CTL_FP32 = 1 };
 
 typedef struct ac_env ac_env_t;
 
@@ -190,10 +197,23 @@ int ac_load_controller(ac_env_t* h, const float* weights, int64_t n);
 /* test access to _inner_rnn_states[agent] (float[128]) and the controller's last output (float[act_low]: 4 control indices (+ bits)) */
 int ac_get_controller_state(ac_env_t* h, int32_t env, int32_t agent, float* hidden, float* low_action);
 int ac_set_controller_state(ac_env_t* h, int32_t env, int32_t agent, const float* hidden);
+/* the form of the handle's controller after AIRCOMBAT_CTL_PRECISION: AC_CTL_FAST or AC_CTL_FP32 (-1 on a null handle) */
+int ac_controller_precision(ac_env_t* h);
+/* The low-level controller on given inputs, no env handle: n calls of BaselineActor's forward, batched, on the device (the kernel bodies of
+ * the env path). x [n][12] in, h [n][128] in/out (GRU state), logits [n][153] out (may be NULL), action [n][4] out (argmax indices); all
+ * host memory. precision: AC_CTL_FAST or AC_CTL_FP32; weights as for ac_load_controller. Synchronous. */
+int ac_controller_forward(int32_t device_id, int32_t precision, const float* weights, int64_t n_weights,
+                          int64_t n, const float* x, float* h, float* logits, int32_t* action);
 /* Host-side check of the arithmetic behind the controller's GEMMs (no GPU, no handle): every fp32 weight and activation is taken apart
  * into two fp16 pieces, hi = fp16(x), lo = fp16(x - hi), |x - hi - lo| <= 2^-22 |x|, and the products run on the fp16 matrix path
  * (controller_pieces.hpp). Writes the two pieces of x[0..n) as float32 values (each with at most 11 significant bits). */
 int ac_split_f16x2(const float* x, int64_t n, float* hi, float* lo);
+/* The same for the AC_CTL_FP32 form (no GPU, no handle): x = b0 + b1 + b2, b0 = bf16(x), b1 = bf16(x - b0), b2 = bf16(x - b0 - b1), each
+ * rounded to nearest-even; the products keep the six terms with i + j <= 2 on the bf16 matrix path. |x - b0 - b1 - b2| <= 2^-24 |x|
+ * (in fact zero) for 2^-103 <= |x| < 2^128 (1 - 2^-9), the range where, under the build's flush-to-zero, every piece is a normal
+ * number and b0 is finite; below 2^-103 the remainder is under 2^-126. Writes the pieces of x[0..n) as float32 values (each with at
+ * most 8 significant bits). */
+int ac_split_bf16x3(const float* x, int64_t n, float* b0, float* b1, float* b2);
 /* Device self-test (needs the GPU, no handle): the closed form the NvN kernels use for MissilePostureReward's agent-by-agent walk over its
  * shared remembered missile (missile_posture_reward.py:18-46) against the round-by-round walk, for every combination of agent states
  * of a 2v2 and a 4v4 env. *mismatches receives the number of combinations that differ (0 = the two agree everywhere). */
