@@ -119,6 +119,16 @@ SIGNATURES = {
     "ac_selftest_missile_walk": (C.c_int, [C.c_int32, _p]),
     "ac_get_controller_state": (C.c_int, [_p, C.c_int32, C.c_int32, _p, _p]),
     "ac_set_controller_state": (C.c_int, [_p, C.c_int32, C.c_int32, _p]),
+    "ac_snapshot_bytes": (C.c_int, [_p, C.POINTER(C.c_int64)]),
+    "ac_snapshot_header": (C.c_int, [_p, _p]),
+    "ac_snapshot_save": (C.c_int, [_p, _p]),
+    "ac_snapshot_load": (C.c_int, [_p, _p]),
+    "ac_snapshot_save_host": (C.c_int, [_p, _p, C.c_int64]),
+    "ac_snapshot_load_host": (C.c_int, [_p, _p, C.c_int64]),
+    "ac_clone_envs": (C.c_int, [_p, _p, _p, C.c_int32]),
+    "ac_snapshot_load_envs": (C.c_int, [_p, _p, _p, C.c_int32]),
+    "ac_get_obs": (C.c_int, [_p, _p]),
+    "ac_snapshot_checksum": (C.c_int, [_p, C.POINTER(C.c_uint64)]),
     "ac_last_error": (C.c_char_p, []),
     "ac_version": (C.c_char_p, []),
     # include/aircombat_buffer.h

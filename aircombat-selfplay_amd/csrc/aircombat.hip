@@ -1685,6 +1685,12 @@ __global__ void reset_all_kernel(DevPtrs P, DevCfg c) {
 // ------------------------------------------------------------------------------------------------ host side (C ABI)
 static thread_local std::string g_err;
 static int fail(const std::string& m) { g_err = m; return -1; }
+// FNV-1a 64 over bytes (the snapshot config digest, snapshot.hpp)
+static uint64_t fnv1a(uint64_t hsh, const void* p, size_t n) {
+  const unsigned char* b = (const unsigned char*)p;
+  for (size_t i = 0; i < n; ++i) { hsh ^= b[i]; hsh *= 0x100000001B3ULL; }
+  return hsh;
+}
 #define HIP_OK(call)                                                                              \
   do {                                                                                            \
     hipError_t e_ = (call);                                                                       \
@@ -1721,6 +1727,14 @@ struct ac_env {
   bool timing;
   bool quad_waves;                       // the 1v1 tasks with munitions up to one workgroup per CU: three FDM waves + the environment wave (FORM 3 / FORM_QUAD)
   bool split_waves;                      // SingleCombat below one wave per SIMD: three waves per 64 aircraft (step_kernel_1v1<.., SPLIT>)
+  // snapshots and clones (snapshot.hpp)
+  uint64_t tmpl_hash, ctl_hash;          // digests of the reset template (computed on first use) and of the weights ac_load_controller took
+  int32_t* h_idx; int32_t* d_idx;        // env index staging, pinned host + device, 2 x idx_cap words
+  int idx_cap;
+  void* h_clone_tab; void* d_clone_tab;  // clone_envs_kernel's section table
+  void* d_snap_hdr;                      // the handle's snapshot header in device memory (ac_snapshot_save copies it)
+  unsigned char snap_hdr[1024];
+  bool snap_hdr_ok;
 };
 
 static void geodetic2ecef_m(double lat_deg, double lon_deg, double alt, double* x, double* y, double* z) {
@@ -2013,6 +2027,17 @@ int ac_create(const ac_config_t* cfg, int32_t n_envs, int32_t device_id, uint64_
   HIP_OK(hipMalloc(&p.done, Npad));
   HIP_OK(hipMalloc(&p.info, sizeof(int) * 4 * (Npad / h->A)));
   p.obs2 = nullptr; p.rew2 = nullptr; p.done2 = nullptr; p.info2 = nullptr;
+  // (every state and output array starts zeroed: a munition slot's words are not all written by a reset, and what a snapshot copies or
+  // ac_snapshot_checksum digests must not depend on what the allocation held before)
+  HIP_OK(hipMemset(p.F, 0, sizeof(float) * NSW * N));
+  HIP_OK(hipMemset(p.D, 0, sizeof(double) * ND * N));
+  HIP_OK(hipMemset(p.MF, 0, sizeof(float) * ms * NMF * N));
+  if (p.MD) HIP_OK(hipMemset(p.MD, 0, sizeof(double) * ms * NMF * N));
+  HIP_OK(hipMemset(p.MI, 0, sizeof(int) * ms * NMI * N));
+  HIP_OK(hipMemset(p.obs, 0, sizeof(float) * Npad * h->obs_dim));
+  HIP_OK(hipMemset(p.rew, 0, sizeof(float) * Npad));
+  HIP_OK(hipMemset(p.done, 0, Npad));
+  HIP_OK(hipMemset(p.info, 0, sizeof(int) * 4 * (Npad / h->A)));
   HIP_OK(hipMalloc(&h->d_actions, sizeof(float) * N * h->act_dim));
   HIP_OK(hipMemset(h->d_actions, 0, sizeof(float) * N * h->act_dim));
   std::vector<float> tab(F16_PACK_LEN);
@@ -2026,6 +2051,8 @@ int ac_create(const ac_config_t* cfg, int32_t n_envs, int32_t device_id, uint64_
   if (scenario) {
     HIP_OK(hipMalloc(&h->d_XF, sizeof(float) * NXF * N));
     HIP_OK(hipMalloc(&h->d_XI, sizeof(int) * NXI * N));
+    HIP_OK(hipMemset(h->d_XF, 0, sizeof(float) * NXF * N));
+    HIP_OK(hipMemset(h->d_XI, 0, sizeof(int) * NXI * N));
   }
   if (heading) {
     HIP_OK(hipMalloc(&h->hp.HD, sizeof(double) * NHD * N));
@@ -2089,12 +2116,15 @@ int ac_destroy(ac_env_t* h) {
   (void)hipSetDevice(h->device);
   (void)hipStreamSynchronize(h->stream);
   void* bufs[] = {h->dp.F, h->dp.D, h->dp.MF, h->dp.MD, h->dp.MI, h->dp.obs, h->dp.rew, h->dp.done, h->dp.info,
-                  h->d_actions, h->d_tab, h->d_tF, h->d_tD, h->d_state_io, h->d_XF, h->d_XI, h->dp.H, h->dp.man_step, h->dp.man_h0, h->d_ctlWs8, h->d_low, h->hp.HD, h->hp.HF, h->hp.HI, h->hp.HR};
+                  h->d_actions, h->d_tab, h->d_tF, h->d_tD, h->d_state_io, h->d_XF, h->d_XI, h->dp.H, h->dp.man_step, h->dp.man_h0, h->d_ctlWs8, h->d_low, h->hp.HD, h->hp.HF, h->hp.HI, h->hp.HR,
+                  h->d_idx, h->d_clone_tab, h->d_snap_hdr};
   for (void* b : bufs) (void)hipFree(b);
   for (int k = 0; k < AC_HOST_SETS; ++k)
     if (h->have_hs[k]) ac_host_set_free(h->hs[k].act, h->hs[k].obs, h->hs[k].rew, h->hs[k].done, h->hs[k].info);   // (a detached set is the caller's)
   if (h->err_host) (void)hipHostFree(h->err_host);
   if (h->count_host) (void)hipHostFree(h->count_host);
+  if (h->h_idx) (void)hipHostFree(h->h_idx);
+  if (h->h_clone_tab) (void)hipHostFree(h->h_clone_tab);
   (void)hipEventDestroy(h->ev0); (void)hipEventDestroy(h->ev1); (void)hipEventDestroy(h->ev_order); (void)hipEventDestroy(h->ev_mid);
   (void)hipStreamDestroy(h->stream);
   delete h;
@@ -2527,6 +2557,8 @@ int ac_load_controller(ac_env_t* h, const float* weights, int64_t n) {
   const std::vector<float> e = h->ctl_np == 3 ? controller_blob<3>(weights) : controller_blob<2>(weights);
   if (!h->d_ctlWs8) HIP_OK(hipMalloc(&h->d_ctlWs8, sizeof(float) * e.size()));
   HIP_OK(hipMemcpy(h->d_ctlWs8, e.data(), sizeof(float) * e.size(), hipMemcpyHostToDevice));
+  h->ctl_hash = fnv1a(0xCBF29CE484222325ULL, weights, sizeof(float) * (size_t)n);   // (part of the snapshot config digest)
+  h->snap_hdr_ok = false;
   return 0;
 }
 int ac_controller_precision(ac_env_t* h) {
@@ -2667,4 +2699,5 @@ int ac_get_missile(ac_env_t* h, int32_t env, int32_t agent, int32_t k, double ou
 
 }  // extern "C"
 
+#include "snapshot.hpp"
 #include "rollout_buffer.hpp"

@@ -26,6 +26,7 @@ import numpy as np
 from .capi import (AcConfig, AC_STATE_LEN, AC_TASK_HEADING, AC_TASK_SINGLECOMBAT, AC_TASK_SHOOT_MISSILE, AC_TASK_MULTICOMBAT, AC_TASK_SCENARIO1,
                    AC_TASK_SCENARIO_NVN, AC_CTL_FAST, AC_CTL_FP32, load_library)
 from .config import config_from_yaml, default_config
+from .snapshot import EnvSnapshot, MultiSnapshot, SnapshotMismatch, check_compatible, decode_header
 
 DONE_MESSAGES = {
     0: "", 1: "altitude is too low", 2: "is on an extreme state", 3: "acceleration is too high", 4: "has been shot down",
@@ -213,6 +214,7 @@ class HipVecEnv:
         handle = C.c_void_p()
         self.lib.check(self.lib.ac_create(C.byref(config), self.num_envs, int(device_id), int(seed), C.byref(handle)), "ac_create")
         self._h = handle
+        self._device_id = int(device_id)
         self.closed = False
         self.waiting = False
         self.obs_dim = self.lib.ac_obs_dim(self._h)
@@ -580,6 +582,132 @@ class HipVecEnv:
         self.lib.check(self.lib.ac_state_checksum(self._h, C.byref(out)), "ac_state_checksum")
         return int(out.value)
 
+    def full_state_checksum(self):
+        """64-bit digest of every array a snapshot holds (ac_snapshot_checksum): the aircraft record, munitions, scenario and heading
+        state, controller state and the last outputs. ``state_checksum`` covers the aircraft record only."""
+        out = C.c_uint64()
+        self.lib.check(self.lib.ac_snapshot_checksum(self._h, C.byref(out)), "ac_snapshot_checksum")
+        return int(out.value)
+
+    # ---- snapshot / restore / clone (include/aircombat.h, ac_snapshot_*)
+    def snapshot_header(self):
+        """The header (decoded) that a snapshot of this handle carries: what a snapshot must match to be restored here."""
+        buf = (C.c_uint8 * 1024)()
+        self.lib.check(self.lib.ac_snapshot_header(self._h, buf), "ac_snapshot_header")
+        return decode_header(bytes(buf))
+
+    def _quiesce(self):
+        if self.waiting:     # a step_async in flight: its results belong to the state being replaced, so they are waited for and dropped
+            self.step_wait()
+
+    def snapshot(self, device=True):
+        """The state of every env as an EnvSnapshot: in a new device buffer (a torch uint8 tensor on this env's GPU; the copy is queued
+        on the handle's stream, after the steps queued so far), or with ``device=False`` in host memory (synchronous). Everything a later
+        step reads is in it; ACMI recording state (``render``) is not env state and is not part of it. A device snapshot carries an
+        event recorded after its copies; ``EnvSnapshot.wait`` waits for it, and ``to_host`` / ``to_bytes`` / ``restore`` call it.
+        The non-finite guard is checked as of the call: a step already completed that went non-finite makes it fail."""
+        self._assert_not_closed()
+        self._quiesce()
+        hdr = self.snapshot_header()
+        if not device:
+            data = np.empty(hdr["total_bytes"], dtype=np.uint8)
+            self.lib.check(self.lib.ac_snapshot_save_host(self._h, data.ctypes.data, data.size), "ac_snapshot_save_host")
+            return EnvSnapshot(hdr, data)
+        import torch
+        dev = torch.device("cuda", self._device_index())
+        data = torch.empty(hdr["total_bytes"], dtype=torch.uint8, device=dev)
+        torch.cuda.current_stream(dev).synchronize()     # (the allocation's stream may still be using recycled memory)
+        self.lib.check(self.lib.ac_snapshot_save(self._h, C.c_void_p(data.data_ptr())), "ac_snapshot_save")
+        # the copies run on the handle's own (non-blocking) stream: an event after them is what every reader of the buffer waits for
+        # (EnvSnapshot.wait: to_host / to_bytes, a restore on any handle, and the snapshot itself before its memory goes back to
+        # torch's allocator; not record_stream: the handle's stream may be destroyed before the tensor is freed)
+        ready = torch.cuda.Event()
+        ready.record(torch.cuda.ExternalStream(self.lib.ac_stream(self._h), device=dev))
+        return EnvSnapshot(hdr, data, ready)
+
+    def _device_index(self):
+        return int(getattr(self, "_device_id", 0))
+
+    def _device_copy(self, snap):
+        """a device-resident form of `snap` (host snapshots are uploaded for the partial restore)."""
+        if snap.on_device:
+            return snap.data
+        import torch
+        dev = torch.device("cuda", self._device_index())
+        d = torch.from_numpy(np.ascontiguousarray(snap.data)).to(dev)
+        torch.cuda.current_stream(dev).synchronize()     # (the upload runs on torch's stream, the restore on the handle's)
+        return d
+
+    def restore(self, snap, envs=None):
+        """Put the state of `snap` back: every env, or only the envs listed in ``envs`` (the others keep theirs, bit for bit). Waits
+        for a pending ``step_async`` first (its results are dropped). Returns the observation after the restore, shaped like
+        ``reset()``'s: that of the snapshot for the restored envs. A snapshot of another task, size, config, seed, controller
+        precision or library version is refused (ValueError) and the state is left as it was. An open ACMI recording is not rewound.
+        A partial restore reads the snapshot on the device: from a host snapshot the WHOLE snapshot is uploaded first (about 490 MB at
+        2^20 aircraft of singlecombat); keep a device snapshot for repeated partial restores."""
+        self._assert_not_closed()
+        if not isinstance(snap, EnvSnapshot):
+            raise TypeError("restore takes an EnvSnapshot (HipVecEnv.snapshot / EnvSnapshot.from_bytes)")
+        self._quiesce()
+        try:
+            check_compatible(snap.header, self.snapshot_header(), "restore")
+        except SnapshotMismatch as exc:
+            raise ValueError(str(exc)) from None
+        if snap.on_device:
+            snap.wait()      # (the save ran on the stream of the handle that took it, this load runs on this handle's)
+        if envs is None:
+            if snap.on_device:
+                self.lib.check(self.lib.ac_snapshot_load(self._h, C.c_void_p(snap.data.data_ptr())), "ac_snapshot_load")
+            else:
+                d = np.ascontiguousarray(snap.data)
+                self.lib.check(self.lib.ac_snapshot_load_host(self._h, d.ctypes.data, d.size), "ac_snapshot_load_host")
+        else:
+            idx, keep = self._indices(envs)
+            if len(keep) == 0:
+                return self._restored_obs()
+            src = self._device_copy(snap)
+            self.lib.check(self.lib.ac_snapshot_load_envs(self._h, C.c_void_p(src.data_ptr()), idx, len(keep)), "ac_snapshot_load_envs")
+            self.sync()   # (an uploaded host snapshot must outlive the copy)
+        return self._restored_obs()
+
+    def _restored_obs(self):
+        obs = np.empty((self.num_envs, self.num_agents, self.obs_dim), dtype=np.float32)
+        self.lib.check(self.lib.ac_get_obs(self._h, obs.ctypes.data), "ac_get_obs")
+        return obs
+
+    def _indices(self, v):
+        """env indices as (pointer, holder): a torch tensor on the device stays there (int32), anything else becomes an int32 numpy array"""
+        if hasattr(v, "data_ptr") and getattr(v, "is_cuda", False):
+            import torch
+            t = v.to(torch.int32).contiguous().reshape(-1)
+            if t.data_ptr() != v.data_ptr():       # (a converted copy is made on torch's stream: done before the handle reads it)
+                torch.cuda.current_stream(t.device).synchronize()
+            return C.c_void_p(t.data_ptr()), t
+        a = np.ascontiguousarray(np.asarray(v, dtype=np.int64).reshape(-1))
+        if a.size and (a.min() < -2**31 or a.max() >= 2**31):
+            raise ValueError("env index out of range")
+        a = a.astype(np.int32)
+        return C.c_void_p(a.ctypes.data), a
+
+    def clone_envs(self, src, dst):
+        """Env ``src[k]`` -> env ``dst[k]`` (every agent, every array a snapshot holds). ``src`` / ``dst``: sequences, numpy arrays or
+        torch tensors (on the device: read after the work queued on the handle's stream, e.g. through ``step_device(stream=...)``).
+        A source may repeat (one engagement into many); a destination may not; a source may not be written by another pair from a
+        different env (a chain or a swap: clone in two calls); and every index must be below ``num_envs`` (ValueError, nothing
+        changed). The scenario tasks draw decoys per env index, so clones of one env part ways at the first chaff-against-missile
+        draw."""
+        self._assert_not_closed()
+        self._quiesce()
+        ps, hs = self._indices(src)
+        pd, hd = self._indices(dst)
+        n = len(hs)
+        if n != len(hd):
+            raise ValueError(f"clone_envs: {n} sources and {len(hd)} destinations")
+        if n == 0:
+            return
+        if self.lib.ac_clone_envs(self._h, ps, pd, n) != 0:
+            raise ValueError(f"ac_clone_envs failed: {self.lib.last_error()}")
+
     def munitions_in_flight(self):
         """Munitions with status LAUNCHED over all envs (ac_munitions_in_flight)."""
         out = C.c_int32()
@@ -609,6 +737,10 @@ class HipShareVecEnv(HipVecEnv):
 
     def reset(self):
         obs = super().reset()
+        return obs, self._share(obs)
+
+    def restore(self, snap, envs=None):
+        obs = super().restore(snap, envs=envs)
         return obs, self._share(obs)
 
     def _extend_set(self, st):
@@ -695,6 +827,25 @@ class MultiDeviceVecEnv:
     def step(self, actions):
         self.step_async(actions)
         return self.step_wait()
+
+    def snapshot(self, device=True):
+        """One EnvSnapshot per part (MultiSnapshot); it restores only onto the same sharding (same parts, same env blocks)."""
+        return MultiSnapshot([p.snapshot(device=device) for p in self.parts], self.blocks)
+
+    def restore(self, snap, envs=None):
+        """HipVecEnv.restore over the parts: every env, or the envs listed in ``envs`` (indices of the whole batch)."""
+        if not isinstance(snap, MultiSnapshot) or [tuple(b) for b in snap.blocks] != [tuple(b) for b in self.blocks]:
+            raise ValueError("restore: the snapshot was taken on another sharding (part count or env blocks differ)")
+        if self._pending is not None:
+            self.step_wait()
+        sel = None if envs is None else np.asarray(envs, dtype=np.int64).reshape(-1)
+        obs = []
+        for p, s, (start, count) in zip(self.parts, snap.parts, self.blocks):
+            mine = None if sel is None else sel[(sel >= start) & (sel < start + count)] - start
+            r = p.restore(s, envs=mine)
+            obs.append(r[0] if self.share else r)
+        obs = np.concatenate(obs, axis=0)
+        return (obs, self._share(obs)) if self.share else obs
 
     def seed(self, seed=None):
         if seed is not None:

@@ -227,6 +227,42 @@ int ac_timing_end(ac_env_t* h, float* total_ms);
  * hierarchical tasks (0 for the control-index form) and the step kernel, each in milliseconds. For the bench's per-kernel rooflines. */
 int ac_step_timed_device(ac_env_t* h, const float* d_actions, float* controller_ms, float* step_ms);
 
+/* Snapshot, restore and clone of the env state (no reference counterpart: the reference's JSBSim processes end with the run).
+ * A snapshot is everything a later step reads that ac_reset does not rebuild from the config: the aircraft record (the 19 groups of
+ * ac_get_state's storage and the fp64 position), every munition slot, the scenario tasks' extension words, the HeadingTask targets,
+ * clocks and numpy-PCG64 states (ac_seed_envs), the hierarchical tasks' GRU state, last low-level action and scripted-opponent
+ * counters, and the last outputs (obs / rewards / dones / info, so a restore hands back the observation of that moment). Layout: a
+ * 1024-byte header (magic "ACSN", format, ac_version(), task, E, A, munition slots, obs_dim, act_dim, controller precision, a
+ * digest of the config, seed, reset template, controller weights and kernel form, the section table), then the arrays in their
+ * device layout, each at a 256-byte boundary. A load refuses a snapshot whose header differs from the handle's; a
+ * fresh handle made with the same config and seed accepts it (resume). Every call is ordered on ac_stream(h). */
+int ac_snapshot_bytes(ac_env_t* h, int64_t* bytes);                 /* size of one whole-batch snapshot */
+int ac_snapshot_header(ac_env_t* h, void* out /* [1024] */);        /* the header a snapshot of this handle carries */
+/* whole batch to / from device memory: one copy per array, stream-ordered on ac_stream(h), no host wait on save; a load reads the
+ * header first (one host wait on ac_stream(h)). The save has finished only for work ordered after it on ac_stream(h): a reader on
+ * any other stream -- a copy to the host, or ac_snapshot_load / ac_snapshot_load_envs on ANOTHER handle, which run on that handle's
+ * stream -- must first be ordered after it (ac_order_before(h, stream), ac_sync(h), or an event recorded on ac_stream(h)).
+ * A save is refused when the non-finite guard has fired in a step that completed before the call; a step still queued ahead of the
+ * save that trips the guard is reported by the next ac_sync / step wait, and the snapshot then holds that state. A whole-batch load
+ * clears the guard (a non-finite state loaded back fires it again at the next step). */
+int ac_snapshot_save(ac_env_t* h, void* d_dst);
+int ac_snapshot_load(ac_env_t* h, const void* d_src);
+/* the same layout in host memory (checkpoint files); synchronous */
+int ac_snapshot_save_host(ac_env_t* h, void* dst, int64_t bytes);
+int ac_snapshot_load_host(ac_env_t* h, const void* src, int64_t bytes);
+/* env src[k] -> env dst[k] for k < n, every agent and array of a snapshot (one gather / scatter kernel). src may repeat (one env
+ * into many), dst may not, no source may be written by another pair from a different env (chains, swaps: clone in two calls),
+ * and every index must be below E: all checked on the host, so the indices (device or host memory)
+ * are read after the work already queued on the stream (one host wait), then the kernel runs stream-ordered. The scenario tasks'
+ * decoy draws are keyed by the env index, so two clones of one env part ways at their first chaff-against-missile draw. */
+int ac_clone_envs(ac_env_t* h, const int32_t* src, const int32_t* dst, int32_t n);
+/* restore only envs idx[0..n) from a whole-batch snapshot in device memory (the same kernel as ac_clone_envs); others untouched */
+int ac_snapshot_load_envs(ac_env_t* h, const void* d_src, const int32_t* idx, int32_t n);
+/* the current observation buffer [E*A][obs_dim] to host memory, after the work queued on the stream */
+int ac_get_obs(ac_env_t* h, float* obs);
+/* 64-bit digest of every array a snapshot holds (ac_state_checksum covers the aircraft record only); test aid */
+int ac_snapshot_checksum(ac_env_t* h, uint64_t* out);
+
 const char* ac_last_error(void);
 const char* ac_version(void);
 
