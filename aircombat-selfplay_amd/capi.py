@@ -129,6 +129,15 @@ SIGNATURES = {
     "ac_snapshot_load_envs": (C.c_int, [_p, _p, _p, C.c_int32]),
     "ac_get_obs": (C.c_int, [_p, _p]),
     "ac_snapshot_checksum": (C.c_int, [_p, C.POINTER(C.c_uint64)]),
+    "ac_policy_blob_floats": (C.c_int, [_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "ac_policy_create": (C.c_int, [C.c_int32, _p, C.POINTER(_p)]),
+    "ac_policy_destroy": (C.c_int, [_p]),
+    "ac_policy_load": (C.c_int, [_p, _p, C.c_int64, _p, C.c_int64]),
+    "ac_policy_load_device": (C.c_int, [_p, _p, _p, C.c_int64, _p, C.c_int64]),
+    "ac_policy_load_refused": (C.c_int, [_p, _p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "ac_policy_packed": (C.c_int, [_p, C.c_int32, C.POINTER(_p), C.POINTER(C.c_int64)]),
+    "ac_policy_get_actions": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, C.c_int32, C.c_uint64, C.c_uint64, _p, _p, _p, _p, _p]),
+    "ac_policy_draw_host": (C.c_int, [C.c_uint64, C.c_uint64, C.c_int64, C.c_int64, C.c_int32, _p]),
     "ac_last_error": (C.c_char_p, []),
     "ac_version": (C.c_char_p, []),
     # include/aircombat_buffer.h

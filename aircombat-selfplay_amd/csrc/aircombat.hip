@@ -2701,3 +2701,5 @@ int ac_get_missile(ac_env_t* h, int32_t env, int32_t agent, int32_t k, double ou
 
 #include "snapshot.hpp"
 #include "rollout_buffer.hpp"
+#include "policy_kernel.hpp"
+#include "policy_host.hpp"

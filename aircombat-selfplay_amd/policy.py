@@ -1,0 +1,338 @@
+"""The reference's PPO rollout policy on the device (``PPOPolicy.get_actions`` / ``.act``, algorithms/ppo/ppo_policy.py).
+
+``DevicePolicy`` runs the actor and critic of the recurrent MLP policy -- hidden sizes ``"128 128"``, one GRU layer of 128, ReLU --
+with its sampling and log-probs in one HIP launch (csrc/policy_kernel.hpp). Supported action spaces: ``MultiDiscrete(nvec)`` with up
+to 160 logits, and ``Tuple(MultiDiscrete(nvec), MultiDiscrete([2, 2, 2, 2]))`` (the four ``BetaShootBernoulli`` munition heads, which
+need ``use_prior``). Everything else raises ``UnsupportedPolicy`` at creation ("The PPO rollout policy").
+
+Sampling is not torch's: a non-deterministic call draws one uniform per (seed, call counter, row, head) from a keyed counter-based
+generator (``draw_host`` recomputes any draw) and picks by inverse CDF. The counter advances by one per call.
+
+Weight blobs (fp32) follow the state_dict tensors in the order ``blob_keys`` lists: actor, then critic.
+"""
+import ctypes as C
+
+import numpy as np
+
+from .capi import load_library, AC_CTL_FAST, AC_CTL_FP32
+
+HID = 128
+
+
+class UnsupportedPolicy(ValueError):
+    """A policy configuration or action space the device kernel does not implement (refused at creation)."""
+
+
+class AcPolicyConfig(C.Structure):
+    _fields_ = [("obs_dim", C.c_int32), ("n_cat", C.c_int32), ("nvec", C.c_int32 * 8), ("n_shoot", C.c_int32), ("single_shoot", C.c_int32),
+                ("hidden_size", C.c_int32 * 2), ("act_hidden_size", C.c_int32 * 2), ("recurrent_hidden_size", C.c_int32),
+                ("recurrent_hidden_layers", C.c_int32), ("activation_id", C.c_int32), ("use_recurrent_policy", C.c_int32),
+                ("use_feature_normalization", C.c_int32), ("use_prior", C.c_int32), ("precision", C.c_int32), ("has_critic", C.c_int32)]
+
+
+class AcPolicyRows(C.Structure):
+    _fields_ = [("n", C.c_int64), ("na", C.c_int32), ("A", C.c_int32), ("a0", C.c_int32), ("act_stride", C.c_int32)]
+
+
+def _sizes(s, what):
+    try:
+        v = [int(x) for x in str(s).split()]
+    except ValueError:
+        raise UnsupportedPolicy(f"unsupported {what} {s!r}")
+    if len(v) != 2:
+        raise UnsupportedPolicy(f"unsupported hidden sizes: {what} {s!r} (only \"128 128\")")
+    return v
+
+
+def _action_heads(act_space):
+    """(nvec, n_shoot, single_shoot) of a gymnasium (or the env's stand-in) action space."""
+    name = type(act_space).__name__
+    if name in ("Box", "_Box"):
+        raise UnsupportedPolicy("unsupported action space Box (DiagGaussian heads)")
+    if name == "MultiBinary":
+        raise UnsupportedPolicy("unsupported action space MultiBinary (Bernoulli heads)")
+    if name in ("Discrete", "_Discrete"):
+        raise UnsupportedPolicy("unsupported action space Discrete")
+    if name in ("MultiDiscrete", "_MultiDiscrete"):
+        return [int(x) for x in np.asarray(act_space.nvec).ravel()], 0, 0
+    if isinstance(act_space, tuple) or name == "Tuple":
+        parts = list(act_space.spaces if hasattr(act_space, "spaces") else act_space)
+        if len(parts) == 2 and type(parts[0]).__name__ in ("MultiDiscrete", "_MultiDiscrete"):
+            nvec = [int(x) for x in np.asarray(parts[0].nvec).ravel()]
+            second = type(parts[1]).__name__
+            if second in ("Discrete", "_Discrete"):
+                return nvec, 0, 1
+            if second in ("MultiDiscrete", "_MultiDiscrete"):
+                mv = [int(x) for x in np.asarray(parts[1].nvec).ravel()]
+                if mv != [2, 2, 2, 2]:
+                    raise UnsupportedPolicy(f"unsupported munition part MultiDiscrete({mv}) (only [2, 2, 2, 2])")
+                return nvec, 4, 0
+    raise UnsupportedPolicy(f"unsupported action space {act_space!r}")
+
+
+def make_config(obs_space, act_space, args, precision="fast", has_critic=True):
+    """The C configuration from the reference's args fields and spaces (no device needed)."""
+    if precision not in ("fast", "fp32"):
+        raise ValueError("precision is 'fast' or 'fp32'")
+    obs_dim = int(np.prod(obs_space.shape))
+    nvec, n_shoot, single = _action_heads(act_space)
+    c = AcPolicyConfig()
+    c.obs_dim = obs_dim
+    c.n_cat = min(len(nvec), 8)
+    for i, n in enumerate(nvec[:8]):
+        c.nvec[i] = n
+    if len(nvec) > 8:
+        c.n_cat = 9   # refused by the library
+    c.n_shoot, c.single_shoot = n_shoot, single
+    c.hidden_size[:] = _sizes(getattr(args, "hidden_size", "128 128"), "hidden_size")
+    c.act_hidden_size[:] = _sizes(getattr(args, "act_hidden_size", "128 128"), "act_hidden_size")
+    c.recurrent_hidden_size = int(getattr(args, "recurrent_hidden_size", 128))
+    c.recurrent_hidden_layers = int(getattr(args, "recurrent_hidden_layers", 1))
+    c.activation_id = int(getattr(args, "activation_id", 1))
+    c.use_recurrent_policy = int(bool(getattr(args, "use_recurrent_policy", True)))
+    c.use_feature_normalization = int(bool(getattr(args, "use_feature_normalization", False)))
+    c.use_prior = int(bool(getattr(args, "use_prior", False)))
+    c.precision = AC_CTL_FP32 if precision == "fp32" else AC_CTL_FAST
+    c.has_critic = int(bool(has_critic))
+    return c
+
+
+def check_config(cfg, lib=None):
+    """Raise UnsupportedPolicy if the library refuses ``cfg``; else (actor floats, critic floats) of the source blobs."""
+    lib = lib or load_library()
+    na, nc = C.c_int64(), C.c_int64()
+    if lib.ac_policy_blob_floats(C.byref(cfg), C.byref(na), C.byref(nc)) != 0:
+        raise UnsupportedPolicy(lib.last_error())
+    return int(na.value), int(nc.value)
+
+
+def _trunk_keys(cfg, prefix_base="base.", prefix_rnn="rnn."):
+    k = []
+    if cfg.use_feature_normalization:
+        k += [prefix_base + "feature_norm.weight", prefix_base + "feature_norm.bias"]
+    for i in (0, 2, 3, 5):
+        k += [f"{prefix_base}mlp.fc.{i}.weight", f"{prefix_base}mlp.fc.{i}.bias"]
+    k += [prefix_rnn + "gru.weight_ih_l0", prefix_rnn + "gru.weight_hh_l0", prefix_rnn + "gru.bias_ih_l0", prefix_rnn + "gru.bias_hh_l0",
+          prefix_rnn + "norm.weight", prefix_rnn + "norm.bias"]
+    return k
+
+
+def blob_keys(cfg):
+    """(actor keys, critic keys): the state_dict tensors of each blob, in blob order."""
+    actor = _trunk_keys(cfg)
+    for i in (0, 2, 3, 5):
+        actor += [f"act.mlp.fc.{i}.weight", f"act.mlp.fc.{i}.bias"]
+    for h in range(cfg.n_cat):
+        actor += [f"act.action_outs.{h}.logits_net.weight", f"act.action_outs.{h}.logits_net.bias"]
+    for s in range(cfg.n_shoot):
+        actor += [f"act.action_outs.{cfg.n_cat + s}.net.weight", f"act.action_outs.{cfg.n_cat + s}.net.bias"]
+    critic = _trunk_keys(cfg)
+    for i in (0, 2, 3, 5):
+        critic += [f"mlp.fc.{i}.weight", f"mlp.fc.{i}.bias"]
+    critic += ["value_out.weight", "value_out.bias"]
+    return actor, critic
+
+
+def _load_sd(sd):
+    if isinstance(sd, (str, bytes)) or hasattr(sd, "__fspath__"):
+        import torch
+        sd = torch.load(sd, map_location="cpu")
+    return sd
+
+
+def blob_from_state_dict(cfg, sd, critic=False):
+    """fp32 numpy blob of one network from its state_dict (torch tensors or arrays)."""
+    keys = blob_keys(cfg)[1 if critic else 0]
+    missing = [k for k in keys if k not in sd]
+    if missing:
+        raise KeyError(f"state_dict lacks {missing[:4]}{' ...' if len(missing) > 4 else ''}")
+    parts = []
+    for k in keys:
+        v = sd[k]
+        v = v.detach().cpu().numpy() if hasattr(v, "detach") else np.asarray(v)
+        parts.append(np.asarray(v, dtype=np.float32).ravel())
+    return np.concatenate(parts)
+
+
+def draw_host(seed, counter, rows, head, lib=None):
+    """The uniforms of rows ``rows`` (a range or an int count) for one head, as the kernel draws them."""
+    lib = lib or load_library()
+    if isinstance(rows, int):
+        rows = range(rows)
+    r0, n = rows.start, len(rows)
+    out = np.empty(n, dtype=np.float32)
+    lib.check(lib.ac_policy_draw_host(C.c_uint64(int(seed) & (2 ** 64 - 1)), C.c_uint64(int(counter) & (2 ** 64 - 1)), int(r0), n,
+                                      int(head), out.ctypes.data), "ac_policy_draw_host")
+    return out
+
+
+class DevicePolicy:
+    """PPOPolicy.get_actions / act on the device (module docstring).
+
+    ``args`` carries the reference's fields ``hidden_size``, ``act_hidden_size``, ``recurrent_hidden_size``, ``recurrent_hidden_layers``,
+    ``activation_id``, ``use_feature_normalization``, ``use_prior`` (and ``use_recurrent_policy``). ``precision``: ``"fast"`` (two fp16
+    pieces per product, AC_CTL_FAST) or ``"fp32"`` (three bf16 pieces, AC_CTL_FP32). ``critic=False`` builds an actor-only policy (a
+    self-play opponent)."""
+
+    def __init__(self, obs_space, act_space, args, device_id=0, precision="fast", seed=0, critic=True):
+        self.lib = load_library()
+        self.cfg = make_config(obs_space, act_space, args, precision, critic)
+        self.actor_floats, self.critic_floats = check_config(self.cfg, self.lib)
+        self.obs_dim = int(self.cfg.obs_dim)
+        self.n_heads = int(self.cfg.n_cat + self.cfg.n_shoot)
+        self.has_critic = bool(critic)
+        self.device_id = int(device_id)
+        self.precision = precision
+        self.seed = int(seed)
+        self.counter = 0
+        h = C.c_void_p()
+        self.lib.check(self.lib.ac_policy_create(self.device_id, C.byref(self.cfg), C.byref(h)), "ac_policy_create")
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self.lib.ac_policy_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    # ---- weights
+    def load_state_dict(self, actor_sd, critic_sd=None):
+        """The reference's state_dicts (or paths of .pt files), host path."""
+        a = blob_from_state_dict(self.cfg, _load_sd(actor_sd))
+        c = blob_from_state_dict(self.cfg, _load_sd(critic_sd), critic=True) if critic_sd is not None else None
+        self.load_blobs(a, c)
+
+    def load_blobs(self, actor, critic=None):
+        a = np.ascontiguousarray(actor, dtype=np.float32)
+        c = None if critic is None else np.ascontiguousarray(critic, dtype=np.float32)
+        self.lib.check(self.lib.ac_policy_load(self._h, a.ctypes.data, a.size, None if c is None else c.ctypes.data,
+                                               0 if c is None else c.size), "ac_policy_load")
+
+    def load_from_torch(self, actor_module, critic_module=None, check=True):
+        """Weights from torch modules (or state_dicts) already on this GPU: concatenated on torch's stream and packed on the device,
+        with no host round trip. A refused load (a non-finite weight; |w| >= 65504 in the fast form) leaves the previous weights in
+        place; with ``check`` it raises (one 8-byte read after the stream)."""
+        import torch
+
+        def dev_blob(m, critic):
+            sd = m.state_dict() if hasattr(m, "state_dict") else m
+            keys = blob_keys(self.cfg)[1 if critic else 0]
+            return torch.cat([sd[k].detach().reshape(-1).to(torch.float32) for k in keys]).contiguous()
+
+        a = dev_blob(actor_module, False)
+        c = dev_blob(critic_module, True) if critic_module is not None else None
+        stream = torch.cuda.current_stream(a.device).cuda_stream
+        self.lib.check(self.lib.ac_policy_load_device(self._h, stream, a.data_ptr(), a.numel(), None if c is None else c.data_ptr(),
+                                                      0 if c is None else c.numel()), "ac_policy_load_device")
+        self._keep = (a, c)   # alive until the packing kernel has run (torch's caching allocator reuses freed blocks in stream order)
+        if check:
+            ra, rc = C.c_int32(), C.c_int32()
+            self.lib.check(self.lib.ac_policy_load_refused(self._h, stream, C.byref(ra), C.byref(rc)), "ac_policy_load_refused")
+            if ra.value or (c is not None and rc.value):
+                raise ValueError("load_from_torch: weights refused (non-finite, or |w| >= 65504 in the fast form); previous weights kept")
+
+    def packed(self, net=0):
+        """The packed weights of the actor (0) / critic (1) as a torch uint8 tensor copy (test aid)."""
+        import torch
+        p, n = C.c_void_p(), C.c_int64()
+        self.lib.check(self.lib.ac_policy_packed(self._h, int(net), C.byref(p), C.byref(n)), "ac_policy_packed")
+        holder = type("_Packed", (), {})()
+        holder.__cuda_array_interface__ = {"shape": (int(n.value) * 4,), "typestr": "|u1", "data": (p.value, False), "version": 2}
+        return torch.as_tensor(holder, device=f"cuda:{self.device_id}").clone()
+
+    # ---- calls
+    def _launch(self, rows, obs, h_a, h_c, masks, deterministic, values, actions, logp, h_a_out, h_c_out, counter):
+        import torch
+        ptr = lambda t: None if t is None else t.data_ptr()
+        stream = torch.cuda.current_stream(torch.device("cuda", self.device_id)).cuda_stream
+        if counter is None:
+            counter = self.counter
+            self.counter += 1
+        self.lib.check(self.lib.ac_policy_get_actions(
+            self._h, stream, C.byref(rows), ptr(obs), ptr(h_a), ptr(h_c), ptr(masks), int(bool(deterministic)),
+            C.c_uint64(self.seed & (2 ** 64 - 1)), C.c_uint64(int(counter) & (2 ** 64 - 1)), ptr(values), ptr(actions), ptr(logp),
+            ptr(h_a_out), ptr(h_c_out)), "ac_policy_get_actions")
+        return counter
+
+    def _tensor(self, x, shape_tail):
+        import torch
+        dev = torch.device("cuda", self.device_id)
+        was_np = not isinstance(x, torch.Tensor)
+        t = torch.as_tensor(np.asarray(x, dtype=np.float32) if was_np else x).to(device=dev, dtype=torch.float32)
+        t = t.reshape((-1,) + shape_tail).contiguous()
+        return t, was_np
+
+    def get_actions(self, obs, rnn_states_actor, rnn_states_critic, masks, deterministic=False, counter=None):
+        """values [N, 1], actions [N, n_heads] (float32), action_log_probs [N, 1], rnn_states_actor / _critic [N, 1, 128] -- like
+        PPOPolicy.get_actions. torch tensors in give torch tensors out (ordered on torch's current stream); numpy in, numpy out."""
+        import torch
+        if not self.has_critic:
+            raise RuntimeError("get_actions: the policy was created without a critic (use act)")
+        o, was_np = self._tensor(obs, (self.obs_dim,))
+        n = o.shape[0]
+        ha, _ = self._tensor(rnn_states_actor, (HID,))
+        hc, _ = self._tensor(rnn_states_critic, (HID,))
+        m, _ = self._tensor(masks, ())
+        if ha.shape[0] != n or hc.shape[0] != n or m.shape[0] != n:
+            raise ValueError("get_actions: obs, rnn states and masks disagree on the number of rows")
+        dev = o.device
+        values = torch.empty((n, 1), device=dev)
+        actions = torch.empty((n, self.n_heads), device=dev)
+        logp = torch.empty((n, 1), device=dev)
+        ha_out = torch.empty((n, 1, HID), device=dev)
+        hc_out = torch.empty((n, 1, HID), device=dev)
+        self.last_counter = self._launch(AcPolicyRows(n, 0, 0, 0, self.n_heads), o, ha, hc, m, deterministic, values, actions, logp,
+                                         ha_out, hc_out, counter)
+        out = (values, actions, logp, ha_out, hc_out)
+        if was_np:
+            torch.cuda.current_stream(dev).synchronize()
+            return tuple(t.cpu().numpy() for t in out)
+        return out
+
+    def act(self, obs, rnn_states_actor, masks, deterministic=False, counter=None, return_log_probs=False):
+        """actions [N, n_heads], rnn_states_actor [N, 1, 128] -- PPOPolicy.act (actor only); with ``return_log_probs`` also the log-probs."""
+        import torch
+        o, was_np = self._tensor(obs, (self.obs_dim,))
+        n = o.shape[0]
+        ha, _ = self._tensor(rnn_states_actor, (HID,))
+        m, _ = self._tensor(masks, ())
+        if ha.shape[0] != n or m.shape[0] != n:
+            raise ValueError("act: obs, rnn states and masks disagree on the number of rows")
+        dev = o.device
+        actions = torch.empty((n, self.n_heads), device=dev)
+        logp = torch.empty((n, 1), device=dev)
+        ha_out = torch.empty((n, 1, HID), device=dev)
+        self.last_counter = self._launch(AcPolicyRows(n, 0, 0, 0, self.n_heads), o, ha, None, m, deterministic, None, actions, logp,
+                                         ha_out, None, counter)
+        out = (actions, ha_out, logp) if return_log_probs else (actions, ha_out)
+        if was_np:
+            torch.cuda.current_stream(dev).synchronize()
+            return tuple(t.cpu().numpy() for t in out)
+        return out
+
+    def act_into_env(self, env, rnn_states, masks, agents=None, deterministic=False, counter=None, rnn_states_out=None):
+        """Actions of agents ``agents`` (a slice [a0, a1) of every env) written straight into ``env``'s device action buffer (ready for
+        ``env.step_device(stream=torch.cuda.current_stream())``), reading their observations from the env's device obs buffer.
+        ``rnn_states`` / ``masks``: torch tensors on the GPU, [E * (a1 - a0), 1, 128] / [E * (a1 - a0), 1], in (env, agent) order; the
+        new states go to ``rnn_states_out`` (default: in place). Returns (rnn_states_out, log-probs [E * (a1 - a0), 1])."""
+        import torch
+        E, A = env.num_envs, env.num_agents
+        a0, a1, step = (agents or slice(0, A)).indices(A)
+        if step != 1 or a1 <= a0:
+            raise ValueError("act_into_env: agents must be a contiguous, non-empty slice")
+        if env.obs_dim != self.obs_dim or env.act_dim < self.n_heads:
+            raise ValueError(f"act_into_env: env obs_dim {env.obs_dim} / act_dim {env.act_dim} do not fit this policy")
+        act, obs, _, _, _ = env.device_tensors()
+        n = E * (a1 - a0)
+        if rnn_states.numel() != n * HID or masks.numel() != n or not rnn_states.is_contiguous() or not masks.is_contiguous():
+            raise ValueError("act_into_env: rnn_states / masks must be contiguous [E * (a1 - a0), 1, 128] / [E * (a1 - a0), 1]")
+        out = rnn_states if rnn_states_out is None else rnn_states_out
+        logp = torch.empty((n, 1), device=obs.device)
+        self.last_counter = self._launch(AcPolicyRows(n, a1 - a0, A, a0, env.act_dim), obs, rnn_states, None, masks, deterministic, None,
+                                         act, logp, out, None, counter)
+        return out, logp

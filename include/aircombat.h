@@ -263,6 +263,51 @@ int ac_get_obs(ac_env_t* h, float* obs);
 /* 64-bit digest of every array a snapshot holds (ac_state_checksum covers the aircraft record only); test aid */
 int ac_snapshot_checksum(ac_env_t* h, uint64_t* out);
 
+/* ---- the PPO rollout policy on the device (PPOPolicy.get_actions / .act of the reference; DESIGN.md, "The PPO rollout policy"). Actor and, optionally,
+ * critic of the recurrent MLP policy (hidden sizes "128 128", GRU 128, ReLU) with MultiDiscrete heads (<= 160 logits) and, optionally,
+ * the four BetaShootBernoulli munition heads of Tuple(MultiDiscrete, MultiDiscrete([2, 2, 2, 2])) with use_prior. Everything else is
+ * refused at creation (ac_last_error names what). */
+typedef struct ac_policy_s ac_policy_t;
+typedef struct {
+  int32_t obs_dim;                      /* 1 .. 32 */
+  int32_t n_cat;                        /* MultiDiscrete heads, 1 .. 8 */
+  int32_t nvec[8];
+  int32_t n_shoot;                      /* 0, or 4: MultiDiscrete([2, 2, 2, 2]) munition heads (need use_prior and obs_dim >= 14) */
+  int32_t single_shoot;                 /* Tuple(MultiDiscrete, Discrete(2)): refused */
+  int32_t hidden_size[2], act_hidden_size[2];   /* 128, 128 */
+  int32_t recurrent_hidden_size, recurrent_hidden_layers;   /* 128, 1 */
+  int32_t activation_id;                /* 1 (ReLU) */
+  int32_t use_recurrent_policy, use_feature_normalization, use_prior;
+  int32_t precision;                    /* AC_CTL_FAST (two fp16 pieces per product) or AC_CTL_FP32 (three bf16 pieces) */
+  int32_t has_critic;
+} ac_policy_config_t;
+/* rows of one call: n rows, or (na > 0) the agent range [a0, a0 + na) of an [E, A, .] obs / action layout with n = E * na; the
+ * action rows are act_stride floats apart. The states, masks, log-probs and values are always compact [n, .]. */
+typedef struct {
+  int64_t n;
+  int32_t na, A, a0, act_stride;
+} ac_policy_rows_t;
+/* lengths of the fp32 source blobs (order: policy_host.hpp / policy.py); no device needed */
+int ac_policy_blob_floats(const ac_policy_config_t* cfg, int64_t* actor_floats, int64_t* critic_floats);
+int ac_policy_create(int32_t device_id, const ac_policy_config_t* cfg, ac_policy_t** out);
+int ac_policy_destroy(ac_policy_t* h);
+/* host blobs (critic may be NULL); refused, leaving the previous weights in place, when a weight is not finite or (fast form) |w| >= 65504 */
+int ac_policy_load(ac_policy_t* h, const float* actor, int64_t n_actor, const float* critic, int64_t n_critic);
+/* device blobs, packed on the device ordered on `stream` (no host round trip); a refused load leaves the previous weights in place and is
+ * reported by ac_policy_load_refused, which waits for the stream */
+int ac_policy_load_device(ac_policy_t* h, void* stream, const float* d_actor, int64_t n_actor, const float* d_critic, int64_t n_critic);
+int ac_policy_load_refused(ac_policy_t* h, void* stream, int32_t* actor_refused, int32_t* critic_refused);
+/* the packed weights of the actor (0) / critic (1) on the device (test aid) */
+int ac_policy_packed(ac_policy_t* h, int32_t net, void** d_ptr, int64_t* floats);
+/* one launch on `stream`: obs, masks [n], GRU states [n, 128] in and out (in place allowed), actions as float32 in the reference's
+ * concatenated head order, log-probs [n] summed over the heads, values [n]. The critic's three pointers all NULL = actor only (.act).
+ * deterministic: the mode; otherwise inverse-CDF draws keyed by (seed, counter, row, head) -- ac_policy_draw_host. */
+int ac_policy_get_actions(ac_policy_t* h, void* stream, const ac_policy_rows_t* rows, const float* d_obs, const float* d_rnn_actor,
+                          const float* d_rnn_critic, const float* d_masks, int32_t deterministic, uint64_t seed, uint64_t counter,
+                          float* d_values, float* d_actions, float* d_logp, float* d_rnn_actor_out, float* d_rnn_critic_out);
+/* the draws of rows row0 .. row0 + nrows - 1, one head, on the host: uniform on [0, 1) in steps of 2^-24 */
+int ac_policy_draw_host(uint64_t seed, uint64_t counter, int64_t row0, int64_t nrows, int32_t head, float* out);
+
 const char* ac_last_error(void);
 const char* ac_version(void);
 

@@ -1,0 +1,201 @@
+"""The tests' float64 torch restatement of the reference's PPO actor / critic (ppo_actor.py, ppo_critic.py, act.py, distributions.py),
+pinned to the reference's own modules by the golden fixtures (test_policy_host.py), and the fixtures' loader.
+
+The fixtures hold what cannot be recomputed without the reference: its outputs, the inputs drawn for them, and the shipped 1v1 actor.
+The seeded case's weights and every case's GRU-state inputs come from `hashed`, an exact integer hash that make_policy_golden.py and
+the tests evaluate alike, so they are not stored."""
+import os
+import types
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+GOLDEN_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+# the two golden cases: (obs_dim, nvec, n_shoot, use_feature_normalization, use_prior, has critic)
+CASES = {"a": (21, [3, 5, 3], 4, False, True, False), "b": (15, [41, 41, 41, 30], 0, True, False, True)}
+FILES = {"a": "policy_1v1.npz", "b": "policy_seeded.npz"}
+# hash streams of the generated arrays
+SEED_RNN, SEED_RNN_CRITIC, SEED_WEIGHTS = 101, 102, 103
+
+
+def hashed(seed, n):
+    """n values uniform on [-1, 1) as float32: splitmix64 of (seed, index) in exact uint64 arithmetic, the same on every platform."""
+    z = np.full(n, seed, dtype=np.uint64) * np.uint64(0x9E3779B97F4A7C15) + np.arange(n, dtype=np.uint64) * np.uint64(0xD1B54A32D192ED03)
+    z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+    z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+    z = z ^ (z >> np.uint64(31))
+    return ((z >> np.uint64(40)).astype(np.float64) * 2.0 ** -23 - 1.0).astype(np.float32)
+
+
+def hashed_states(seed, n):
+    return hashed(seed, n * 128).reshape(n, 1, 128)
+
+
+def seeded_state_dicts(obs_dim, nvec, use_fn, seed=SEED_WEIGHTS):
+    """Actor and critic weights of the seeded case in the reference's state_dict layout: Linear weights and biases uniform on
+    +-1/sqrt(fan_in) (torch's default bound), LayerNorm scales 1 +- 0.2 and shifts +- 0.2, one hash stream per tensor."""
+    def lin(pre, o, i, k):
+        b = np.float32(1.0 / np.sqrt(i))
+        return {pre + "weight": (hashed(seed * 1000 + k, o * i) * b).reshape(o, i), pre + "bias": hashed(seed * 1000 + k + 500, o) * b}
+
+    def ln(pre, n, k):
+        return {pre + "weight": np.float32(1.0) + np.float32(0.2) * hashed(seed * 1000 + k, n), pre + "bias": np.float32(0.2) * hashed(seed * 1000 + k + 500, n)}
+
+    def trunk(k0):
+        d = ln("base.feature_norm.", obs_dim, k0) if use_fn else {}
+        d.update(lin("base.mlp.fc.0.", 128, obs_dim, k0 + 1)); d.update(ln("base.mlp.fc.2.", 128, k0 + 2))
+        d.update(lin("base.mlp.fc.3.", 128, 128, k0 + 3)); d.update(ln("base.mlp.fc.5.", 128, k0 + 4))
+        b = np.float32(1.0 / np.sqrt(128))
+        d["rnn.gru.weight_ih_l0"] = (hashed(seed * 1000 + k0 + 5, 384 * 128) * b).reshape(384, 128)
+        d["rnn.gru.weight_hh_l0"] = (hashed(seed * 1000 + k0 + 6, 384 * 128) * b).reshape(384, 128)
+        d["rnn.gru.bias_ih_l0"] = hashed(seed * 1000 + k0 + 7, 384) * b
+        d["rnn.gru.bias_hh_l0"] = hashed(seed * 1000 + k0 + 8, 384) * b
+        d.update(ln("rnn.norm.", 128, k0 + 9))
+        return d, k0 + 10
+
+    a, k = trunk(0)
+    for pre in ("act.mlp.fc.",):
+        a.update(lin(pre + "0.", 128, 128, k)); a.update(ln(pre + "2.", 128, k + 1))
+        a.update(lin(pre + "3.", 128, 128, k + 2)); a.update(ln(pre + "5.", 128, k + 3))
+    for h, n in enumerate(nvec):
+        a.update(lin(f"act.action_outs.{h}.logits_net.", n, 128, k + 4 + h))
+    c, k = trunk(100)
+    c.update(lin("mlp.fc.0.", 128, 128, k)); c.update(ln("mlp.fc.2.", 128, k + 1))
+    c.update(lin("mlp.fc.3.", 128, 128, k + 2)); c.update(ln("mlp.fc.5.", 128, k + 3))
+    c.update(lin("value_out.", 1, 128, k + 4))
+    return a, c
+
+
+def golden_case(tag):
+    """One case as a dict: the stored arrays plus the generated ones (GRU-state inputs, the seeded weights as ``sd`` / ``critic_sd``,
+    ``probs`` = the softmax of each head's stored logits)."""
+    z = np.load(os.path.join(GOLDEN_DIR, FILES[tag]))
+    g = {k: z[k] for k in z.files if "/" not in k}
+    obs_dim, nvec, n_shoot, fn, _, has_c = CASES[tag]
+    n = len(g["obs"])
+    g["rnn_states"] = hashed_states(SEED_RNN, n)
+    g["masks"] = g["masks"].astype(np.float32)
+    g["actions"] = g["actions"].astype(np.float64)
+    if has_c:
+        g["rnn_states_critic"] = hashed_states(SEED_RNN_CRITIC, n)
+        g["sd"], g["critic_sd"] = seeded_state_dicts(obs_dim, nvec, fn)
+    else:
+        g["sd"], g["critic_sd"] = {k[3:]: z[k] for k in z.files if k.startswith("sd/")}, None
+    lg, off, probs = g["logits"].astype(np.float64), 0, []
+    for k in nvec:
+        e = np.exp(lg[:, off:off + k] - lg[:, off:off + k].max(-1, keepdims=True))
+        probs.append(e / e.sum(-1, keepdims=True))
+        off += k
+    g["probs"] = np.concatenate(probs, -1)
+    return g
+
+
+def golden():
+    """Both cases in one dict, keys prefixed with the case tag (``a_obs``, ``b_values``, ...)."""
+    return {f"{tag}_{k}": v for tag in CASES for k, v in golden_case(tag).items()}
+
+
+def state_dicts(g, tag):
+    """(actor state_dict, critic state_dict or None) of a case, as numpy arrays in state_dict order."""
+    return g[f"{tag}_sd"], g[f"{tag}_critic_sd"]
+
+
+def spaces(tag):
+    from importlib import import_module
+    ve = import_module("aircombat-selfplay_amd.vec_env")
+    obs_dim, nvec, n_shoot = CASES[tag][:3]
+    obs = ve._Box(-10, 10, (obs_dim,))
+    act = ve._Tuple([ve._MultiDiscrete(nvec), ve._MultiDiscrete([2] * 4)]) if n_shoot else ve._MultiDiscrete(nvec)
+    return obs, act
+
+
+def args(tag):
+    _, _, _, fn, prior, _ = CASES[tag]
+    return types.SimpleNamespace(hidden_size="128 128", act_hidden_size="128 128", recurrent_hidden_size=128, recurrent_hidden_layers=1,
+                                 activation_id=1, use_feature_normalization=fn, use_prior=prior, use_recurrent_policy=True)
+
+
+def _t(x):
+    return torch.as_tensor(np.asarray(x, dtype=np.float64))
+
+
+def _mlp(sd, prefix, x):
+    for i in (0, 3):
+        x = F.relu(x @ _t(sd[f"{prefix}{i}.weight"]).T + _t(sd[f"{prefix}{i}.bias"]))
+        x = F.layer_norm(x, (x.shape[-1],), _t(sd[f"{prefix}{i + 2}.weight"]), _t(sd[f"{prefix}{i + 2}.bias"]), 1e-5)
+    return x
+
+
+def _trunk(sd, obs, rnn, masks, use_fn):
+    x = _t(obs)
+    if use_fn:
+        x = F.layer_norm(x, (x.shape[-1],), _t(sd["base.feature_norm.weight"]), _t(sd["base.feature_norm.bias"]), 1e-5)
+    x = _mlp(sd, "base.mlp.fc.", x)
+    h = _t(rnn).reshape(-1, 128) * _t(masks).reshape(-1, 1)
+    gi = x @ _t(sd["rnn.gru.weight_ih_l0"]).T + _t(sd["rnn.gru.bias_ih_l0"])
+    gh = h @ _t(sd["rnn.gru.weight_hh_l0"]).T + _t(sd["rnn.gru.bias_hh_l0"])
+    r = torch.sigmoid(gi[:, :128] + gh[:, :128])
+    z = torch.sigmoid(gi[:, 128:256] + gh[:, 128:256])
+    n = torch.tanh(gi[:, 256:] + r * gh[:, 256:])
+    hn = (1 - z) * n + z * h
+    x = F.layer_norm(hn, (128,), _t(sd["rnn.norm.weight"]), _t(sd["rnn.norm.bias"]), 1e-5)
+    return x, hn
+
+
+def prior(obs):
+    o = _t(obs)
+    ang, dist = torch.rad2deg(o[:, 11]), o[:, 13] * 10000
+    a0 = torch.full((o.shape[0],), 3.0, dtype=torch.float64)
+    b0 = torch.full((o.shape[0],), 10.0, dtype=torch.float64)
+    a0[dist <= 12000] = 6
+    a0[dist <= 8000] = 10
+    b0[ang <= 45] = 6
+    b0[ang <= 22.5] = 3
+    return a0, b0
+
+
+def actor(sd, obs, rnn, masks, nvec, n_shoot, use_fn):
+    """Deterministic actor outputs: dict of actions, log_probs, rnn_states_out, logits, probs, shoot_p (float64 numpy)."""
+    x, hn = _trunk(sd, obs, rnn, masks, use_fn)
+    x = _mlp(sd, "act.mlp.fc.", x)
+    logits = [x @ _t(sd[f"act.action_outs.{i}.logits_net.weight"]).T + _t(sd[f"act.action_outs.{i}.logits_net.bias"]) for i in range(len(nvec))]
+    acts, lps = [], []
+    for l in logits:
+        a = l.argmax(-1)
+        acts.append(a.double())
+        lps.append(torch.log_softmax(l, -1).gather(-1, a[:, None])[:, 0])
+    out = {"logits": torch.cat(logits, -1).numpy(), "probs": torch.cat([torch.softmax(l, -1) for l in logits], -1).numpy()}
+    if n_shoot:
+        a0, b0 = prior(obs)
+        ps = []
+        for s in range(n_shoot):
+            k = len(nvec) + s
+            y = x @ _t(sd[f"act.action_outs.{k}.net.weight"]).T + _t(sd[f"act.action_outs.{k}.net.bias"])
+            y = 100 - F.softplus(100 - F.softplus(y))
+            al, be = 1 + y[:, 0], 1 + y[:, 1]
+            p = (al + a0) / (al + a0 + be + b0)
+            ps.append(p)
+            fire = (p > 0.5).float()   # FixedBernoulli.mode() is float32, and log_prob then runs at the value's precision
+            acts.append(fire.double())
+            lps.append(torch.distributions.Bernoulli(probs=p).log_prob(fire).double())
+        out["shoot_p"] = torch.stack(ps, -1).numpy()
+    out["actions"] = torch.stack(acts, -1).numpy()
+    out["log_probs"] = torch.stack(lps, -1).sum(-1, keepdim=True).numpy()
+    out["rnn_states_out"] = hn[:, None, :].numpy()
+    return out
+
+
+def critic(sd, obs, rnn, masks, use_fn):
+    x, hn = _trunk(sd, obs, rnn, masks, use_fn)
+    x = _mlp(sd, "mlp.fc.", x)
+    v = x @ _t(sd["value_out.weight"]).T + _t(sd["value_out.bias"])
+    return {"values": v.numpy(), "rnn_states_critic_out": hn[:, None, :].numpy()}
+
+
+def inverse_cdf(probs, u):
+    """The kernel's pick: the first index whose running sum exceeds u (probs sum to 1), and the distance of u to the nearest CDF edge."""
+    c = np.cumsum(probs, -1)
+    pick = np.minimum((c <= u[:, None]).sum(-1), probs.shape[-1] - 1)
+    edge = np.min(np.abs(np.concatenate([np.zeros((len(u), 1)), c], -1) - u[:, None]), -1)
+    return pick, edge
