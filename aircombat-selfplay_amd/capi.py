@@ -96,6 +96,7 @@ SIGNATURES = {
     "ac_step_async_device": (C.c_int, [_p, _p]),
     "ac_device_buffers": (C.c_int, [_p, C.POINTER(_p), C.POINTER(_p), C.POINTER(_p), C.POINTER(_p), C.POINTER(_p)]),
     "ac_stream": (_p, [_p]),
+    "ac_dispatch_path": (C.c_char_p, [_p]),
     "ac_sync": (C.c_int, [_p]),
     "ac_get_state": (C.c_int, [_p, C.c_int32, C.c_int32, C.POINTER(C.c_double)]),
     "ac_set_state": (C.c_int, [_p, C.c_int32, C.c_int32, C.POINTER(C.c_double)]),

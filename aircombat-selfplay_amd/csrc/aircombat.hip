@@ -17,6 +17,7 @@
 #include <vector>
 #include <cmath>
 #include <algorithm>
+#include <chrono>
 #include "../../include/aircombat.h"
 #include "../../include/aircombat_buffer.h"
 #include "clk_stamps.hpp"
@@ -1697,6 +1698,8 @@ static uint64_t fnv1a(uint64_t hsh, const void* p, size_t n) {
     if (e_ != hipSuccess) return fail(std::string(#call) + ": " + hipGetErrorString(e_));        \
   } while (0)
 
+#include "aql_dispatch.hpp"
+
 struct ac_env {
   ac_config_t cfg;
   DevCfg dc;
@@ -1735,6 +1738,9 @@ struct ac_env {
   void* d_snap_hdr;                      // the handle's snapshot header in device memory (ac_snapshot_save copies it)
   unsigned char snap_hdr[1024];
   bool snap_hdr_ok;
+  // host steps as AQL packets on a queue of the handle's own (aql_dispatch.hpp)
+  AqlState aql;
+  bool stream_dirty;                     // work enqueued on `stream` since it was last synchronised: the next AQL dispatch synchronises it
 };
 
 static void geodetic2ecef_m(double lat_deg, double lon_deg, double alt, double* x, double* y, double* z) {
@@ -1763,14 +1769,30 @@ static int ctl_rows_pin() {
   const char* cr = getenv("AIRCOMBAT_CTL_ROWS");
   return cr ? (atoi(cr) == 64 ? 64 : 32) : 0;
 }
-static int launch_step(ac_env* h, const float* d_actions, int host_set = -1) {
+// The kernel(s) of one step, chosen from the handle's task, kernel form and grid, with their arguments packed as the kernarg segment holds
+// them. launch_step launches the plan through HIP; a host step on the AQL path dispatches the same plan (aql_dispatch.hpp).
+static int step_plan(ac_env* h, const float* d_actions, int host_set, StepPlan* sp) {
   DevPtrs p = h->dp;
   p.actions = d_actions ? d_actions : h->d_actions;
   if (host_set >= 0) {   // actions read from, and a second copy of every output written to, mapped host memory
     const ac_env::HostSet& hs = h->hs[host_set];
     p.actions = hs.act; p.obs2 = hs.obs; p.rew2 = hs.rew; p.done2 = hs.done; p.info2 = hs.info;
   }
-  dim3 block(64), grid((h->N + 63) / 64);
+  sp->n = 0;
+  const dim3 block(64), grid((h->N + 63) / 64);
+  auto add = [&](const void* fn, dim3 g, dim3 b) -> KLaunch& {
+    KLaunch& k = sp->k[sp->n++];
+    k.fn = fn; k.grid = g; k.block = b; k.size = 0; k.argc = 0;
+    return k;
+  };
+  // the three argument lists of the step kernel families
+  auto pd = [&](const void* fn, dim3 b) { KLaunch& k = add(fn, grid, b); k.arg(p); k.arg(h->dc); };
+  auto scen = [&](const void* fn, dim3 b) {
+    KLaunch& k = add(fn, grid, b);
+    k.arg(p); k.arg(h->dc); k.arg(h->d_XF); k.arg(h->d_XI); k.arg((const float*)nullptr); k.arg((const int*)nullptr);
+  };
+  auto heading = [&](const void* fn, dim3 b) { KLaunch& k = add(fn, grid, b); k.arg(p); k.arg(h->dc); k.arg(h->hp); k.arg(h->hc); k.arg((int)0); };
+#define AC_K(...) reinterpret_cast<const void*>(&__VA_ARGS__)
   if (h->cfg.hierarchical) {   // [3,5,3] (+ weapon bits) -> control indices, then the ordinary step on those
     if (!h->d_ctlWs8) return fail("hierarchical task: ac_load_controller has not been called");
     ctl::Args a{h->d_ctlWs8, p.actions, p.obs, p.H, h->d_low, h->N, h->obs_dim, h->act_dim, h->act_low,
@@ -1781,81 +1803,118 @@ static int launch_step(ac_env* h, const float* d_actions, int host_set = -1) {
         // after the other, 64 beyond (AIRCOMBAT_CTL_ROWS pins it for tests)
       const int rows = ctl_rows_for(h->N, h->ctl_rows);
       const dim3 g8((h->N + rows - 1) / rows);
+      const void* fn;
       if (h->ctl_np == 3) {   // the reference-precision form (three bf16 pieces)
-        if (rows == 64) {
-          if (h->cfg.use_baseline) hipLaunchKernelGGL((controller8x3_kernel<true, 4>), g8, dim3(512), 0, h->stream, a);
-          else hipLaunchKernelGGL((controller8x3_kernel<false, 4>), g8, dim3(512), 0, h->stream, a);
-        } else if (h->cfg.use_baseline) hipLaunchKernelGGL((controller8x3_kernel<true, 2>), g8, dim3(512), 0, h->stream, a);
-        else hipLaunchKernelGGL((controller8x3_kernel<false, 2>), g8, dim3(512), 0, h->stream, a);
-      } else if (rows == 64) {
-        if (h->cfg.use_baseline) hipLaunchKernelGGL((controller8_kernel<true, 4>), g8, dim3(512), 0, h->stream, a);
-        else hipLaunchKernelGGL((controller8_kernel<false, 4>), g8, dim3(512), 0, h->stream, a);
-      } else if (h->cfg.use_baseline) hipLaunchKernelGGL((controller8_kernel<true, 2>), g8, dim3(512), 0, h->stream, a);
-      else hipLaunchKernelGGL((controller8_kernel<false, 2>), g8, dim3(512), 0, h->stream, a);
+        if (rows == 64) fn = h->cfg.use_baseline ? AC_K(controller8x3_kernel<true, 4>) : AC_K(controller8x3_kernel<false, 4>);
+        else fn = h->cfg.use_baseline ? AC_K(controller8x3_kernel<true, 2>) : AC_K(controller8x3_kernel<false, 2>);
+      } else if (rows == 64) fn = h->cfg.use_baseline ? AC_K(controller8_kernel<true, 4>) : AC_K(controller8_kernel<false, 4>);
+      else fn = h->cfg.use_baseline ? AC_K(controller8_kernel<true, 2>) : AC_K(controller8_kernel<false, 2>);
+      add(fn, g8, dim3(512)).arg(a);
     }
-    HIP_OK(hipGetLastError());
-    if (h->mark_mid) HIP_OK(hipEventRecord(h->ev_mid, h->stream));
     p.actions = h->d_low;
   }
   const bool one_wave_per_simd = grid.x <= 1024;  // 256 CUs x 4 SIMDs
-  if (h->cfg.task == AC_TASK_HEADING) {
-    if (h->split_waves) hipLaunchKernelGGL(step_kernel_heading<true>, grid, dim3(192), 0, h->stream, p, h->dc, h->hp, h->hc, 0);
-    else if (one_wave_per_simd) hipLaunchKernelGGL((step_kernel_heading<false, 1>), grid, block, 0, h->stream, p, h->dc, h->hp, h->hc, 0);
-    else hipLaunchKernelGGL((step_kernel_heading<false, 2>), grid, block, 0, h->stream, p, h->dc, h->hp, h->hc, 0);
-    HIP_OK(hipGetLastError());
-    return 0;
-  }
   // pair form (every task with munitions): two waves per workgroup, so one wave per SIMD up to 512 workgroups
   const bool pair_wpe1 = grid.x <= 512;
   const bool gun_only = h->cfg.task == AC_TASK_WVR || h->cfg.task == AC_TASK_MANEUVER;
-  if (gun_only) {   // the scenario kernel family without munitions: ticks only between the env steps
-    if (h->split_waves) hipLaunchKernelGGL((step_kernel_scenario<2, 1, FORM_SPLIT>), grid, dim3(192), 0, h->stream, p, h->dc, h->d_XF, h->d_XI, nullptr, nullptr);
-    else if (pair_wpe1) hipLaunchKernelGGL((step_kernel_scenario<2, 1, FORM_PAIR>), grid, dim3(128), 0, h->stream, p, h->dc, h->d_XF, h->d_XI, nullptr, nullptr);
-    else hipLaunchKernelGGL((step_kernel_scenario<2, 2, FORM_PAIR>), grid, dim3(128), 0, h->stream, p, h->dc, h->d_XF, h->d_XI, nullptr, nullptr);
+  if (h->cfg.task == AC_TASK_HEADING) {
+    if (h->split_waves) heading(AC_K(step_kernel_heading<true>), dim3(192));
+    else if (one_wave_per_simd) heading(AC_K(step_kernel_heading<false, 1>), block);
+    else heading(AC_K(step_kernel_heading<false, 2>), block);
+  } else if (gun_only) {   // the scenario kernel family without munitions: ticks only between the env steps
+    if (h->split_waves) scen(AC_K(step_kernel_scenario<2, 1, FORM_SPLIT>), dim3(192));
+    else if (pair_wpe1) scen(AC_K(step_kernel_scenario<2, 1, FORM_PAIR>), dim3(128));
+    else scen(AC_K(step_kernel_scenario<2, 2, FORM_PAIR>), dim3(128));
   } else if (h->cfg.task == AC_TASK_DODGE_MISSILE && h->A > 2) {   // multiplecombat_dodge_missile: the scenario kernel family's NvN pair form, DODGE build
-#define AC_LAUNCH_DODGE(AA)                                                                                                                                     \
-  do {                                                                                                                                                          \
-    if (pair_wpe1) hipLaunchKernelGGL((step_kernel_scenario<AA, 1, FORM_PAIR, true>), grid, dim3(128), 0, h->stream, p, h->dc, h->d_XF, h->d_XI, nullptr, nullptr); \
-    else hipLaunchKernelGGL((step_kernel_scenario<AA, 2, FORM_PAIR, true>), grid, dim3(128), 0, h->stream, p, h->dc, h->d_XF, h->d_XI, nullptr, nullptr);          \
-  } while (0)
-    if (h->A == 4) AC_LAUNCH_DODGE(4); else AC_LAUNCH_DODGE(8);
-#undef AC_LAUNCH_DODGE
+    if (h->A == 4) scen(pair_wpe1 ? AC_K(step_kernel_scenario<4, 1, FORM_PAIR, true>) : AC_K(step_kernel_scenario<4, 2, FORM_PAIR, true>), dim3(128));
+    else scen(pair_wpe1 ? AC_K(step_kernel_scenario<8, 1, FORM_PAIR, true>) : AC_K(step_kernel_scenario<8, 2, FORM_PAIR, true>), dim3(128));
   } else if (h->cfg.task == AC_TASK_SCENARIO1 || h->cfg.task == AC_TASK_SCENARIO_NVN) {
-#define AC_LAUNCH_PAIR(AA)                                                                                                                                \
-  do {                                                                                                                                                    \
-    if (pair_wpe1) hipLaunchKernelGGL((step_kernel_scenario<AA, 1, FORM_PAIR>), grid, dim3(128), 0, h->stream, p, h->dc, h->d_XF, h->d_XI, nullptr, nullptr); \
-    else hipLaunchKernelGGL((step_kernel_scenario<AA, 2, FORM_PAIR>), grid, dim3(128), 0, h->stream, p, h->dc, h->d_XF, h->d_XI, nullptr, nullptr);          \
-  } while (0)
     // (the quad form for the 1v1 scenario only: for 2v2 / 4v4 it takes fewer cycles than the pair form and more time -- with four busy
     // waves per CU and the fp64 munitions of four or eight aircraft the part clocks lower, 1.8 against 2.05 GHz)
-    if (h->A == 2 && h->quad_waves) hipLaunchKernelGGL((step_kernel_scenario<2, 1, FORM_QUAD>), grid, dim3(256), 0, h->stream, p, h->dc, h->d_XF, h->d_XI, nullptr, nullptr);
-    else if (h->A == 2) AC_LAUNCH_PAIR(2); else if (h->A == 4) AC_LAUNCH_PAIR(4); else AC_LAUNCH_PAIR(8);
-#undef AC_LAUNCH_PAIR
+    if (h->A == 2 && h->quad_waves) scen(AC_K(step_kernel_scenario<2, 1, FORM_QUAD>), dim3(256));
+    else if (h->A == 2) scen(pair_wpe1 ? AC_K(step_kernel_scenario<2, 1, FORM_PAIR>) : AC_K(step_kernel_scenario<2, 2, FORM_PAIR>), dim3(128));
+    else if (h->A == 4) scen(pair_wpe1 ? AC_K(step_kernel_scenario<4, 1, FORM_PAIR>) : AC_K(step_kernel_scenario<4, 2, FORM_PAIR>), dim3(128));
+    else scen(pair_wpe1 ? AC_K(step_kernel_scenario<8, 1, FORM_PAIR>) : AC_K(step_kernel_scenario<8, 2, FORM_PAIR>), dim3(128));
   } else if (h->cfg.task == AC_TASK_MULTICOMBAT) {
-    if (h->split_waves) {
-      if (h->A == 4) hipLaunchKernelGGL((step_kernel_nvn<4, 1, true>), grid, dim3(192), 0, h->stream, p, h->dc);
-      else hipLaunchKernelGGL((step_kernel_nvn<8, 1, true>), grid, dim3(192), 0, h->stream, p, h->dc);
-    } else if (h->A == 4) {
-      if (one_wave_per_simd) hipLaunchKernelGGL((step_kernel_nvn<4, 1>), grid, block, 0, h->stream, p, h->dc);
-      else hipLaunchKernelGGL((step_kernel_nvn<4, 2>), grid, block, 0, h->stream, p, h->dc);
-    } else {
-      if (one_wave_per_simd) hipLaunchKernelGGL((step_kernel_nvn<8, 1>), grid, block, 0, h->stream, p, h->dc);
-      else hipLaunchKernelGGL((step_kernel_nvn<8, 2>), grid, block, 0, h->stream, p, h->dc);
-    }
+    if (h->split_waves) pd(h->A == 4 ? AC_K(step_kernel_nvn<4, 1, true>) : AC_K(step_kernel_nvn<8, 1, true>), dim3(192));
+    else if (h->A == 4) pd(one_wave_per_simd ? AC_K(step_kernel_nvn<4, 1>) : AC_K(step_kernel_nvn<4, 2>), block);
+    else pd(one_wave_per_simd ? AC_K(step_kernel_nvn<8, 1>) : AC_K(step_kernel_nvn<8, 2>), block);
   } else if (h->cfg.task == AC_TASK_SINGLECOMBAT) {
-    if (h->split_waves) hipLaunchKernelGGL((step_kernel_1v1<AC_TASK_SINGLECOMBAT, 1, 1>), grid, dim3(192), 0, h->stream, p, h->dc);
-    else if (one_wave_per_simd) hipLaunchKernelGGL((step_kernel_1v1<AC_TASK_SINGLECOMBAT, 1, 0>), grid, block, 0, h->stream, p, h->dc);
-    else hipLaunchKernelGGL((step_kernel_1v1<AC_TASK_SINGLECOMBAT, 2, 0>), grid, block, 0, h->stream, p, h->dc);
+    if (h->split_waves) pd(AC_K(step_kernel_1v1<AC_TASK_SINGLECOMBAT, 1, 1>), dim3(192));
+    else if (one_wave_per_simd) pd(AC_K(step_kernel_1v1<AC_TASK_SINGLECOMBAT, 1, 0>), block);
+    else pd(AC_K(step_kernel_1v1<AC_TASK_SINGLECOMBAT, 2, 0>), block);
   } else if (h->cfg.task == AC_TASK_DODGE_MISSILE) {
-    if (h->quad_waves) hipLaunchKernelGGL((step_kernel_1v1<AC_TASK_DODGE_MISSILE, 1, 3>), grid, dim3(256), 0, h->stream, p, h->dc);
-    else if (pair_wpe1) hipLaunchKernelGGL((step_kernel_1v1<AC_TASK_DODGE_MISSILE, 1, 2>), grid, dim3(128), 0, h->stream, p, h->dc);
-    else hipLaunchKernelGGL((step_kernel_1v1<AC_TASK_DODGE_MISSILE, 2, 2>), grid, dim3(128), 0, h->stream, p, h->dc);
+    if (h->quad_waves) pd(AC_K(step_kernel_1v1<AC_TASK_DODGE_MISSILE, 1, 3>), dim3(256));
+    else if (pair_wpe1) pd(AC_K(step_kernel_1v1<AC_TASK_DODGE_MISSILE, 1, 2>), dim3(128));
+    else pd(AC_K(step_kernel_1v1<AC_TASK_DODGE_MISSILE, 2, 2>), dim3(128));
   } else {
-    if (h->quad_waves) hipLaunchKernelGGL((step_kernel_1v1<AC_TASK_SHOOT_MISSILE, 1, 3>), grid, dim3(256), 0, h->stream, p, h->dc);
-    else if (pair_wpe1) hipLaunchKernelGGL((step_kernel_1v1<AC_TASK_SHOOT_MISSILE, 1, 2>), grid, dim3(128), 0, h->stream, p, h->dc);
-    else hipLaunchKernelGGL((step_kernel_1v1<AC_TASK_SHOOT_MISSILE, 2, 2>), grid, dim3(128), 0, h->stream, p, h->dc);
+    if (h->quad_waves) pd(AC_K(step_kernel_1v1<AC_TASK_SHOOT_MISSILE, 1, 3>), dim3(256));
+    else if (pair_wpe1) pd(AC_K(step_kernel_1v1<AC_TASK_SHOOT_MISSILE, 1, 2>), dim3(128));
+    else pd(AC_K(step_kernel_1v1<AC_TASK_SHOOT_MISSILE, 2, 2>), dim3(128));
   }
-  HIP_OK(hipGetLastError());
+#undef AC_K
+  for (int i = 0; i < sp->n; ++i)
+    if (sp->k[i].size > KLaunch::kCap) return fail("step_plan: kernel arguments larger than the kernarg block");
+  return 0;
+}
+static int launch_plan(ac_env* h, const StepPlan& sp) {   // through HIP, on the handle's stream
+  h->stream_dirty = true;
+  for (int i = 0; i < sp.n; ++i) {
+    const KLaunch& k = sp.k[i];
+    HIP_OK(hipLaunchKernel(k.fn, k.grid, k.block, const_cast<void**>(k.argv), 0, h->stream));
+    if (i + 1 < sp.n && h->mark_mid) HIP_OK(hipEventRecord(h->ev_mid, h->stream));   // (between the controller and the step kernel)
+  }
+  return 0;
+}
+static int launch_step(ac_env* h, const float* d_actions, int host_set = -1) {
+  StepPlan sp;
+  if (step_plan(h, d_actions, host_set, &sp)) return -1;
+  return launch_plan(h, sp);
+}
+// ---- the two directions of ordering between the handle's HIP stream and its AQL queue (aql_dispatch.hpp)
+static int aql_fault(ac_env* h, const std::string& e) {   // a queue that has faulted or timed out is not used again
+  h->aql.set_hip("fallback: " + e);
+  return fail(e);
+}
+// An AQL step still in flight is waited for: every entry point that touches the stream or the state calls this first (host_entry).
+static int aql_settle(ac_env* h) {
+  if (!h->aql.in_flight) return 0;
+  const std::string e = aql_wait(&h->aql);
+  return e.empty() ? 0 : aql_fault(h, e);
+}
+// HIP work enqueued on the stream since it was last synchronised is complete before an AQL dispatch (never on a rollout's steady state).
+static int stream_settle(ac_env* h) {
+  if (!h->stream_dirty) return 0;
+  HIP_OK(hipStreamSynchronize(h->stream));
+  h->stream_dirty = false;
+  return 0;
+}
+// Entry of every C entry point that enqueues on h->stream or reads / writes the state outside a host step.
+static int host_entry(ac_env* h) {
+  if (aql_settle(h)) return -1;
+  h->stream_dirty = true;
+  return 0;
+}
+// A host step: through the AQL queue once it is set up (and no timing bracket is open: bench.py times host steps with HIP events on the
+// stream), else through HIP; the first host step of a handle goes through HIP and sets the queue up after it.
+static int host_step(ac_env* h, int set) {
+  if (aql_settle(h)) return -1;
+  StepPlan sp;
+  if (step_plan(h, nullptr, set, &sp)) return -1;
+  AqlState& a = h->aql;
+  bool aql = a.mode == AqlState::READY && !h->timing && sp.n == a.nkern;
+  for (int i = 0; aql && i < sp.n; ++i) aql = sp.k[i].fn == a.kern[i].fn;
+  if (aql) {
+    if (stream_settle(h)) return -1;
+    const std::string e = aql_dispatch(&a, sp, set);
+    return e.empty() ? 0 : aql_fault(h, e);
+  }
+  if (launch_plan(h, sp)) return -1;
+  if (a.mode == AqlState::PENDING && !h->timing) {   // the launch above has loaded HIP's code object: its kernel symbols can be resolved
+    const std::string e = aql_setup(&a, h->device, sp);
+    if (e.empty()) a.mode = AqlState::READY;
+    else { aql_release(&a); a.set_hip("fallback: " + e); }
+  }
   return 0;
 }
 static int launch_reset(ac_env* h) {
@@ -1941,6 +2000,10 @@ int ac_create(const ac_config_t* cfg, int32_t n_envs, int32_t device_id, uint64_
   ac_env* h = new ac_env();
   memset(h, 0, sizeof *h);
   h->cfg = *cfg; h->E = n_envs; h->A = cfg->n_agents; h->N = n_envs * cfg->n_agents; h->device = device_id;
+  {   // AIRCOMBAT_DISPATCH=hip pins host steps to the HIP runtime (A/B runs, tests); the default dispatches them as AQL packets
+    const char* d = getenv("AIRCOMBAT_DISPATCH");
+    if (d && !strcmp(d, "hip")) h->aql.set_hip("AIRCOMBAT_DISPATCH=hip");
+  }
   h->cfg.controller_precision = cfg->hierarchical ? ctl_prec : AC_CTL_FAST;
   h->ctl_np = h->cfg.controller_precision == AC_CTL_FP32 ? 3 : 2;
   {  // Kernel form. Tasks whose substeps are the FDM tick alone: three waves per 64 aircraft (split_kernel.hpp) while the chip has
@@ -2114,6 +2177,8 @@ int ac_create(const ac_config_t* cfg, int32_t n_envs, int32_t device_id, uint64_
 int ac_destroy(ac_env_t* h) {
   if (!h) return 0;
   (void)hipSetDevice(h->device);
+  (void)aql_settle(h);
+  aql_release(&h->aql);          // the AQL queue, its signal and the kernarg blocks
   (void)hipStreamSynchronize(h->stream);
   void* bufs[] = {h->dp.F, h->dp.D, h->dp.MF, h->dp.MD, h->dp.MI, h->dp.obs, h->dp.rew, h->dp.done, h->dp.info,
                   h->d_actions, h->d_tab, h->d_tF, h->d_tD, h->d_state_io, h->d_XF, h->d_XI, h->dp.H, h->dp.man_step, h->dp.man_h0, h->d_ctlWs8, h->d_low, h->hp.HD, h->hp.HF, h->hp.HI, h->hp.HR,
@@ -2137,6 +2202,7 @@ int ac_num_agents(const ac_env_t* h) { return h ? h->A : -1; }
 
 int ac_reset(ac_env_t* h, float* obs) {
   if (!h) return fail("ac_reset: null handle");
+  if (host_entry(h)) return -1;
   HIP_OK(hipSetDevice(h->device));
   HIP_OK(hipStreamSynchronize(h->stream));    // (a step still in flight may yet write the error word)
   *h->err_host = 0; h->err_sticky = 0;
@@ -2148,6 +2214,7 @@ int ac_reset(ac_env_t* h, float* obs) {
 
 int ac_step(ac_env_t* h, const float* actions, float* obs, float* rewards, uint8_t* dones, int32_t* info) {
   if (!h || !actions) return fail("ac_step: null argument");
+  if (host_entry(h)) return -1;
   HIP_OK(hipSetDevice(h->device));
   const size_t N = (size_t)h->N;
   HIP_OK(hipMemcpyAsync(h->d_actions, actions, sizeof(float) * N * h->act_dim, hipMemcpyHostToDevice, h->stream));
@@ -2191,6 +2258,7 @@ int ac_host_buffers(ac_env_t* h, int32_t set, float** actions, float** obs, floa
 // env_wrappers.py:276-282): the handle gives the set up -- ac_destroy leaves it alone -- and the holder frees it when the last array is gone.
 int ac_host_set_detach(ac_env_t* h, int32_t set) {
   if (!h || set < 0 || set >= AC_HOST_SETS || !h->have_hs[set]) return fail("ac_host_set_detach: no such set");
+  if (host_entry(h)) return -1;
   HIP_OK(hipSetDevice(h->device));
   HIP_OK(hipStreamSynchronize(h->stream));     // no step may still be writing into it
   h->have_hs[set] = false;
@@ -2204,13 +2272,18 @@ int ac_step_host_async(ac_env_t* h, int32_t set) {
   if (!h || set < 0 || set >= AC_HOST_SETS) return fail("ac_step_host_async: bad argument");
   if (!h->have_hs[set]) return fail("ac_step_host_async: call ac_host_buffers for this set first");
   HIP_OK(hipSetDevice(h->device));
-  return launch_step(h, nullptr, set);
+  return host_step(h, set);
 }
 int ac_step_host_wait(ac_env_t* h) {
   if (!h) return fail("ac_step_host_wait: null handle");
-  // (hipStreamSynchronize spins on the completion signal itself; polling hipStreamQuery measured 5 us slower per step,
-  //  tools/micro/host_io.hip)
-  HIP_OK(hipStreamSynchronize(h->stream));
+  if (h->aql.in_flight) {   // a busy-wait on the packet's completion signal (aql_dispatch.hpp)
+    if (aql_settle(h)) return -1;
+  } else {
+    // (hipStreamSynchronize spins on the completion signal itself; polling hipStreamQuery measured 5 us slower per step,
+    //  tools/micro/host_io.hip)
+    HIP_OK(hipStreamSynchronize(h->stream));
+    h->stream_dirty = false;
+  }
   return check_nonfinite(h, "ac_step_host_wait");
 }
 int ac_step_host(ac_env_t* h, int32_t set) {   // step_async + step_wait in one call (VecEnv.step, env_wrappers.py:30-42)
@@ -2222,6 +2295,7 @@ int ac_step_host(ac_env_t* h, int32_t set) {   // step_async + step_wait in one 
 // policy writing the actions, a buffer reading the observations) is not ordered against the step kernel unless asked for.
 int ac_order_after(ac_env_t* h, void* producer_stream) {   // the next step waits for everything queued on producer_stream so far
   if (!h) return fail("ac_order_after: null handle");
+  if (host_entry(h)) return -1;
   HIP_OK(hipSetDevice(h->device));
   HIP_OK(hipEventRecord(h->ev_order, (hipStream_t)producer_stream));
   HIP_OK(hipStreamWaitEvent(h->stream, h->ev_order, 0));
@@ -2229,6 +2303,7 @@ int ac_order_after(ac_env_t* h, void* producer_stream) {   // the next step wait
 }
 int ac_order_before(ac_env_t* h, void* consumer_stream) {  // consumer_stream waits for every step queued so far
   if (!h) return fail("ac_order_before: null handle");
+  if (host_entry(h)) return -1;
   HIP_OK(hipSetDevice(h->device));
   HIP_OK(hipEventRecord(h->ev_order, h->stream));
   HIP_OK(hipStreamWaitEvent((hipStream_t)consumer_stream, h->ev_order, 0));
@@ -2237,6 +2312,7 @@ int ac_order_before(ac_env_t* h, void* consumer_stream) {  // consumer_stream wa
 
 int ac_step_async_device(ac_env_t* h, const float* d_actions) {
   if (!h) return fail("ac_step_async_device: null handle");
+  if (host_entry(h)) return -1;
   HIP_OK(hipSetDevice(h->device));
   return launch_step(h, d_actions);
 }
@@ -2249,20 +2325,38 @@ int ac_device_buffers(ac_env_t* h, float** d_actions, float** d_obs, float** d_r
   if (d_info) *d_info = h->dp.info;
   return 0;
 }
-void* ac_stream(ac_env_t* h) { return h ? (void*)h->stream : nullptr; }
+void* ac_stream(ac_env_t* h) {   // (the caller may enqueue on it: a host step still in flight is waited for first)
+  if (!h) return nullptr;
+  (void)host_entry(h);
+  return (void*)h->stream;
+}
+const char* ac_dispatch_path(ac_env_t* h) {
+  if (!h) return "";
+  switch (h->aql.mode) {
+    case AqlState::READY: return "aql";
+    case AqlState::PENDING: return "pending";     // (the first host step goes through HIP and sets the queue up)
+    default: return h->aql.why;                   // "AIRCOMBAT_DISPATCH=hip" or "fallback: <reason>"
+  }
+}
 int ac_sync(ac_env_t* h) {
   if (!h) return fail("ac_sync: null handle");
+  if (host_entry(h)) return -1;
   HIP_OK(hipSetDevice(h->device));
   HIP_OK(hipStreamSynchronize(h->stream));
+  h->stream_dirty = false;
   return check_nonfinite(h, "ac_sync");
 }
 int ac_timing_begin(ac_env_t* h) {
   if (!h) return fail("ac_timing_begin: null handle");
+  if (host_entry(h)) return -1;
   HIP_OK(hipEventRecord(h->ev0, h->stream));
+  h->timing = true;      // host steps take the HIP path until ac_timing_end: the events time what is launched on the stream
   return 0;
 }
 int ac_timing_end(ac_env_t* h, float* total_ms) {
   if (!h || !total_ms) return fail("ac_timing_end: null argument");
+  if (host_entry(h)) return -1;
+  h->timing = false;
   HIP_OK(hipEventRecord(h->ev1, h->stream));
   HIP_OK(hipEventSynchronize(h->ev1));
   HIP_OK(hipEventElapsedTime(total_ms, h->ev0, h->ev1));
@@ -2271,6 +2365,7 @@ int ac_timing_end(ac_env_t* h, float* total_ms) {
 
 int ac_step_timed_device(ac_env_t* h, const float* d_actions, float* controller_ms, float* step_ms) {
   if (!h || !controller_ms || !step_ms) return fail("ac_step_timed_device: null argument");
+  if (host_entry(h)) return -1;
   HIP_OK(hipSetDevice(h->device));
   HIP_OK(hipEventRecord(h->ev0, h->stream));
   h->mark_mid = h->cfg.hierarchical != 0;
@@ -2328,6 +2423,7 @@ static SlotMap slot_map() {
 }
 int ac_get_state(ac_env_t* h, int32_t env, int32_t agent, double* out) {
   if (check_idx(h, env, agent) || !out) return fail("ac_get_state: bad argument");
+  if (host_entry(h)) return -1;
   HIP_OK(hipSetDevice(h->device));
   const size_t N = h->N, n = (size_t)env * h->A + agent;
   double io[kStateIoWords];
@@ -2353,6 +2449,7 @@ int ac_get_state(ac_env_t* h, int32_t env, int32_t agent, double* out) {
 }
 int ac_set_state(ac_env_t* h, int32_t env, int32_t agent, const double* in) {
   if (check_idx(h, env, agent) || !in) return fail("ac_set_state: bad argument");
+  if (host_entry(h)) return -1;
   HIP_OK(hipSetDevice(h->device));
   const size_t N = h->N, n = (size_t)env * h->A + agent;
   HIP_OK(hipMemcpyAsync(h->d_state_io, in, sizeof(double) * (ND + NF + NI), hipMemcpyHostToDevice, h->stream));
@@ -2363,6 +2460,7 @@ int ac_set_state(ac_env_t* h, int32_t env, int32_t agent, const double* in) {
 }
 int ac_set_status(ac_env_t* h, int32_t env, int32_t agent, int32_t status) {
   if (check_idx(h, env, agent)) return -1;
+  if (host_entry(h)) return -1;
   if (status < AC_ALIVE || status > AC_SHOTDOWN) return fail("ac_set_status: bad status");
   HIP_OK(hipSetDevice(h->device));
   HIP_OK(hipStreamSynchronize(h->stream));
@@ -2386,6 +2484,7 @@ __global__ void entity_kernel(DevPtrs P, DevCfg c, int n, double* out) {
 }
 int ac_get_entity(ac_env_t* h, int32_t env, int32_t agent, double out[12]) {
   if (check_idx(h, env, agent) || !out) return fail("ac_get_entity: bad argument");
+  if (host_entry(h)) return -1;
   HIP_OK(hipSetDevice(h->device));
   double* d_out = h->d_state_io;   // (the handle's scratch record: no allocation per call)
   hipLaunchKernelGGL(entity_kernel, dim3(1), dim3(64), 0, h->stream, h->dp, h->dc, env * h->A + agent, d_out);
@@ -2423,6 +2522,7 @@ __global__ void state_checksum_kernel(DevPtrs P, DevCfg c, unsigned long long* o
 }
 int ac_state_checksum(ac_env_t* h, uint64_t* out) {
   if (!h || !out) return fail("ac_state_checksum: null argument");
+  if (host_entry(h)) return -1;
   HIP_OK(hipSetDevice(h->device));
   unsigned long long* d_out;
   HIP_OK(hipMalloc(&d_out, sizeof(unsigned long long)));
@@ -2451,6 +2551,7 @@ __global__ void munitions_in_flight_kernel(DevPtrs P, DevCfg c, int* out) {
 }
 int ac_munitions_in_flight(ac_env_t* h, int32_t* count) {
   if (!h || !count) return fail("ac_munitions_in_flight: null argument");
+  if (host_entry(h)) return -1;
   *count = 0;
   if (!h->dc.msl_slots || !h->dp.MI) return 0;
   HIP_OK(hipSetDevice(h->device));
@@ -2466,6 +2567,7 @@ int ac_munitions_in_flight(ac_env_t* h, int32_t* count) {
 }
 int ac_seed_envs(ac_env_t* h, const uint64_t* states) {
   if (!h || !states) return fail("ac_seed_envs: null argument");
+  if (host_entry(h)) return -1;
   if (h->cfg.task != AC_TASK_HEADING) return fail("ac_seed_envs: only AC_TASK_HEADING draws from env.np_random");
   HIP_OK(hipSetDevice(h->device));
   HIP_OK(hipStreamSynchronize(h->stream));
@@ -2478,6 +2580,7 @@ int ac_seed_envs(ac_env_t* h, const uint64_t* states) {
 }
 int ac_get_heading_state(ac_env_t* h, int32_t env, double out[8]) {
   if (check_idx(h, env, 0) || !out) return fail("ac_get_heading_state: bad argument");
+  if (host_entry(h)) return -1;
   if (h->cfg.task != AC_TASK_HEADING) return fail("ac_get_heading_state: not an AC_TASK_HEADING handle");
   HIP_OK(hipSetDevice(h->device));
   HIP_OK(hipStreamSynchronize(h->stream));
@@ -2550,6 +2653,7 @@ static int controller_weights_ok(const char* who, int np, const float* weights, 
 extern "C" {
 int ac_load_controller(ac_env_t* h, const float* weights, int64_t n) {
   if (!h || !weights) return fail("ac_load_controller: null argument");
+  if (host_entry(h)) return -1;
   if (!h->cfg.hierarchical) return fail("ac_load_controller: the handle was not created with cfg.hierarchical");
   if (controller_weights_ok("ac_load_controller", h->ctl_np, weights, n)) return -1;
   HIP_OK(hipSetDevice(h->device));
@@ -2653,6 +2757,7 @@ int ac_selftest_missile_walk(int32_t device_id, int32_t* mismatches) {
 }
 int ac_get_controller_state(ac_env_t* h, int32_t env, int32_t agent, float* hidden, float* low_action) {
   if (check_idx(h, env, agent)) return fail("ac_get_controller_state: bad argument");
+  if (host_entry(h)) return -1;
   if (!h->cfg.hierarchical) return fail("ac_get_controller_state: not a hierarchical handle");
   HIP_OK(hipSetDevice(h->device));
   HIP_OK(hipStreamSynchronize(h->stream));
@@ -2663,6 +2768,7 @@ int ac_get_controller_state(ac_env_t* h, int32_t env, int32_t agent, float* hidd
 }
 int ac_set_controller_state(ac_env_t* h, int32_t env, int32_t agent, const float* hidden) {
   if (check_idx(h, env, agent) || !hidden) return fail("ac_set_controller_state: bad argument");
+  if (host_entry(h)) return -1;
   if (!h->cfg.hierarchical) return fail("ac_set_controller_state: not a hierarchical handle");
   HIP_OK(hipSetDevice(h->device));
   HIP_OK(hipStreamSynchronize(h->stream));
@@ -2672,6 +2778,7 @@ int ac_set_controller_state(ac_env_t* h, int32_t env, int32_t agent, const float
 }
 int ac_get_missile(ac_env_t* h, int32_t env, int32_t agent, int32_t k, double out[12]) {
   if (check_idx(h, env, agent) || !out) return fail("ac_get_missile: bad argument");
+  if (host_entry(h)) return -1;
   if (k < 0 || k >= h->dc.msl_slots) return fail("ac_get_missile: no such missile slot");
   HIP_OK(hipSetDevice(h->device));
   HIP_OK(hipStreamSynchronize(h->stream));

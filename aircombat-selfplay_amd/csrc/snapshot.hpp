@@ -282,6 +282,7 @@ extern "C" {
 
 int ac_snapshot_bytes(ac_env_t* h, int64_t* bytes) {
   if (!h || !bytes) return fail("ac_snapshot_bytes: null argument");
+  if (host_entry(h)) return -1;
   AcSnapHeader hd;
   if (snap_header(h, &hd)) return -1;
   *bytes = (int64_t)hd.total_bytes;
@@ -290,6 +291,7 @@ int ac_snapshot_bytes(ac_env_t* h, int64_t* bytes) {
 
 int ac_snapshot_header(ac_env_t* h, void* out) {
   if (!h || !out) return fail("ac_snapshot_header: null argument");
+  if (host_entry(h)) return -1;
   HIP_OK(hipSetDevice(h->device));
   AcSnapHeader hd;
   if (snap_header(h, &hd)) return -1;
@@ -305,6 +307,7 @@ static int snap_healthy(ac_env* h, const char* who) {
 
 int ac_snapshot_save(ac_env_t* h, void* d_dst) {
   if (!h || !d_dst) return fail("ac_snapshot_save: null argument");
+  if (host_entry(h)) return -1;
   HIP_OK(hipSetDevice(h->device));
   if (snap_healthy(h, "ac_snapshot_save")) return -1;
   if (!h->snap_hdr_ok) {   // the header is constant per handle (until ac_load_controller): built and uploaded once
@@ -326,6 +329,7 @@ int ac_snapshot_save(ac_env_t* h, void* d_dst) {
 
 int ac_snapshot_save_host(ac_env_t* h, void* dst, int64_t bytes) {
   if (!h || !dst) return fail("ac_snapshot_save_host: null argument");
+  if (host_entry(h)) return -1;
   HIP_OK(hipSetDevice(h->device));
   AcSnapHeader hd;
   if (snap_header(h, &hd)) return -1;
@@ -345,6 +349,7 @@ static void snap_clear_guard(ac_env* h) { *(volatile int*)h->err_host = 0; h->er
 
 int ac_snapshot_load(ac_env_t* h, const void* d_src) {
   if (!h || !d_src) return fail("ac_snapshot_load: null argument");
+  if (host_entry(h)) return -1;
   HIP_OK(hipSetDevice(h->device));
   AcSnapHeader got;
   HIP_OK(hipMemcpyAsync(&got, d_src, sizeof got, hipMemcpyDeviceToHost, h->stream));
@@ -359,6 +364,7 @@ int ac_snapshot_load(ac_env_t* h, const void* d_src) {
 
 int ac_snapshot_load_host(ac_env_t* h, const void* src, int64_t bytes) {
   if (!h || !src) return fail("ac_snapshot_load_host: null argument");
+  if (host_entry(h)) return -1;
   HIP_OK(hipSetDevice(h->device));
   if (bytes < (int64_t)sizeof(AcSnapHeader)) return fail("ac_snapshot_load_host: shorter than a snapshot header");
   AcSnapHeader got;
@@ -376,6 +382,7 @@ int ac_snapshot_load_host(ac_env_t* h, const void* src, int64_t bytes) {
 
 int ac_clone_envs(ac_env_t* h, const int32_t* src, const int32_t* dst, int32_t n) {
   if (!h || !src || !dst) return fail("ac_clone_envs: null argument");
+  if (host_entry(h)) return -1;
   HIP_OK(hipSetDevice(h->device));
   if (snap_stage_indices(h, src, dst, n, "ac_clone_envs")) return -1;
   return snap_launch_clone(h, nullptr, nullptr, n);
@@ -383,6 +390,7 @@ int ac_clone_envs(ac_env_t* h, const int32_t* src, const int32_t* dst, int32_t n
 
 int ac_snapshot_load_envs(ac_env_t* h, const void* d_src, const int32_t* idx, int32_t n) {
   if (!h || !d_src || !idx) return fail("ac_snapshot_load_envs: null argument");
+  if (host_entry(h)) return -1;
   HIP_OK(hipSetDevice(h->device));
   AcSnapHeader got;
   HIP_OK(hipMemcpyAsync(&got, d_src, sizeof got, hipMemcpyDeviceToHost, h->stream));
@@ -394,6 +402,7 @@ int ac_snapshot_load_envs(ac_env_t* h, const void* d_src, const int32_t* idx, in
 
 int ac_get_obs(ac_env_t* h, float* obs) {
   if (!h || !obs) return fail("ac_get_obs: null argument");
+  if (host_entry(h)) return -1;
   HIP_OK(hipSetDevice(h->device));
   HIP_OK(hipMemcpyAsync(obs, h->dp.obs, sizeof(float) * (size_t)h->N * h->obs_dim, hipMemcpyDeviceToHost, h->stream));
   HIP_OK(hipStreamSynchronize(h->stream));
@@ -402,6 +411,7 @@ int ac_get_obs(ac_env_t* h, float* obs) {
 
 int ac_snapshot_checksum(ac_env_t* h, uint64_t* out) {
   if (!h || !out) return fail("ac_snapshot_checksum: null argument");
+  if (host_entry(h)) return -1;
   HIP_OK(hipSetDevice(h->device));
   unsigned long long* d_out;
   HIP_OK(hipMalloc(&d_out, sizeof(unsigned long long)));
