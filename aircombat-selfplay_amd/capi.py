@@ -14,6 +14,7 @@ AC_TASK_HEADING, AC_TASK_SINGLECOMBAT, AC_TASK_DODGE_MISSILE, AC_TASK_SHOOT_MISS
 AC_TASK_SCENARIO1, AC_TASK_SCENARIO_NVN, AC_TASK_WVR, AC_TASK_MANEUVER = 5, 6, 7, 8
 AC_ALIVE, AC_CRASH, AC_SHOTDOWN = 0, 1, 2
 AC_CTL_FAST, AC_CTL_FP32 = 0, 1   # AcConfig.controller_precision: the low-level controller's arithmetic
+AC_CENT_EXPLICIT, AC_CENT_ENV_SHARE = 0, 1   # the MAPPO critic's input: explicit cent_obs rows, or each env's obs block (include/aircombat.h)
 
 
 class HipExtensionMissing(RuntimeError):
@@ -139,6 +140,10 @@ SIGNATURES = {
     "ac_policy_packed": (C.c_int, [_p, C.c_int32, C.POINTER(_p), C.POINTER(C.c_int64)]),
     "ac_policy_get_actions": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, C.c_int32, C.c_uint64, C.c_uint64, _p, _p, _p, _p, _p]),
     "ac_policy_draw_host": (C.c_int, [C.c_uint64, C.c_uint64, C.c_int64, C.c_int64, C.c_int32, _p]),
+    "ac_policy_mappo_blob_floats": (C.c_int, [_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "ac_policy_mappo_create": (C.c_int, [C.c_int32, _p, C.POINTER(_p)]),
+    "ac_policy_get_actions_mappo": (C.c_int, [_p, _p, _p, _p, _p, C.c_int32, _p, _p, _p, C.c_int32, C.c_uint64, C.c_uint64, _p, _p, _p, _p, _p]),
+    "ac_policy_get_values": (C.c_int, [_p, _p, _p, _p, C.c_int32, _p, _p, _p, _p]),
     "ac_last_error": (C.c_char_p, []),
     "ac_version": (C.c_char_p, []),
     # include/aircombat_buffer.h

@@ -9,12 +9,15 @@ Sampling is not torch's: a non-deterministic call draws one uniform per (seed, c
 generator (``draw_host`` recomputes any draw) and picks by inverse CDF. The counter advances by one per call.
 
 Weight blobs (fp32) follow the state_dict tensors in the order ``blob_keys`` lists: actor, then critic.
+
+``DeviceMAPPOPolicy`` is the MAPPO form (algorithms/mappo/ppo_policy.py): the same actor, with input widths up to 640, and a critic on
+``cent_obs`` / ``share_obs`` (up to 640 wide), fed either explicit rows or, straight from an env, each env's whole observation block.
 """
 import ctypes as C
 
 import numpy as np
 
-from .capi import load_library, AC_CTL_FAST, AC_CTL_FP32
+from .capi import load_library, AC_CTL_FAST, AC_CTL_FP32, AC_CENT_EXPLICIT, AC_CENT_ENV_SHARE
 
 HID = 128
 
@@ -28,6 +31,10 @@ class AcPolicyConfig(C.Structure):
                 ("hidden_size", C.c_int32 * 2), ("act_hidden_size", C.c_int32 * 2), ("recurrent_hidden_size", C.c_int32),
                 ("recurrent_hidden_layers", C.c_int32), ("activation_id", C.c_int32), ("use_recurrent_policy", C.c_int32),
                 ("use_feature_normalization", C.c_int32), ("use_prior", C.c_int32), ("precision", C.c_int32), ("has_critic", C.c_int32)]
+
+
+class AcPolicyMappoConfig(C.Structure):
+    _fields_ = [("base", AcPolicyConfig), ("cent_obs_dim", C.c_int32)]
 
 
 class AcPolicyRows(C.Structure):
@@ -102,6 +109,23 @@ def check_config(cfg, lib=None):
     lib = lib or load_library()
     na, nc = C.c_int64(), C.c_int64()
     if lib.ac_policy_blob_floats(C.byref(cfg), C.byref(na), C.byref(nc)) != 0:
+        raise UnsupportedPolicy(lib.last_error())
+    return int(na.value), int(nc.value)
+
+
+def make_mappo_config(obs_space, cent_obs_space, act_space, args, precision="fast", has_critic=True):
+    """The MAPPO configuration: make_config's fields plus the critic's input width."""
+    c = AcPolicyMappoConfig()
+    c.base = make_config(obs_space, act_space, args, precision, has_critic)
+    c.cent_obs_dim = int(np.prod(cent_obs_space.shape))
+    return c
+
+
+def check_mappo_config(cfg, lib=None):
+    """check_config for an AcPolicyMappoConfig: UnsupportedPolicy naming the field, else the blob lengths."""
+    lib = lib or load_library()
+    na, nc = C.c_int64(), C.c_int64()
+    if lib.ac_policy_mappo_blob_floats(C.byref(cfg), C.byref(na), C.byref(nc)) != 0:
         raise UnsupportedPolicy(lib.last_error())
     return int(na.value), int(nc.value)
 
@@ -294,6 +318,31 @@ class DevicePolicy:
             return tuple(t.cpu().numpy() for t in out)
         return out
 
+    def get_values(self, obs, rnn_states_critic, masks):
+        """values [N, 1] -- PPOPolicy.get_values: the critic alone (one launch of critic workgroups), bit-identical to get_actions' values."""
+        o, was_np = self._tensor(obs, (self.obs_dim,))
+        return self._values(AcPolicyRows(o.shape[0], 0, 0, 0, self.n_heads), o, AC_CENT_EXPLICIT, rnn_states_critic, masks, was_np)
+
+    def _values(self, rows, inp, mode, rnn_states_critic, masks, was_np, rnn_states_out=None):
+        import torch
+        if not self.has_critic:
+            raise RuntimeError("get_values: the policy was created without a critic")
+        n = int(rows.n)
+        hc, _ = self._tensor(rnn_states_critic, (HID,))
+        m, _ = self._tensor(masks, ())
+        if hc.shape[0] != n or m.shape[0] != n:
+            raise ValueError("get_values: inputs, rnn states and masks disagree on the number of rows")
+        values = torch.empty((n, 1), device=hc.device)
+        hc_out = torch.empty((n, 1, HID), device=hc.device) if rnn_states_out is None else rnn_states_out
+        stream = torch.cuda.current_stream(hc.device).cuda_stream
+        self.lib.check(self.lib.ac_policy_get_values(self._h, stream, C.byref(rows), inp.data_ptr(), int(mode), hc.data_ptr(), m.data_ptr(),
+                                                     values.data_ptr(), hc_out.data_ptr()), "ac_policy_get_values")
+        self._keep_values = (inp, hc, m)   # (the inputs stay alive until the launch has run: torch frees in stream order)
+        if was_np:
+            torch.cuda.current_stream(hc.device).synchronize()
+            return values.cpu().numpy()
+        return values
+
     def act(self, obs, rnn_states_actor, masks, deterministic=False, counter=None, return_log_probs=False):
         """actions [N, n_heads], rnn_states_actor [N, 1, 128] -- PPOPolicy.act (actor only); with ``return_log_probs`` also the log-probs."""
         import torch
@@ -336,3 +385,122 @@ class DevicePolicy:
         self.last_counter = self._launch(AcPolicyRows(n, a1 - a0, A, a0, env.act_dim), obs, rnn_states, None, masks, deterministic, None,
                                          act, logp, out, None, counter)
         return out, logp
+
+
+class DeviceMAPPOPolicy(DevicePolicy):
+    """The MAPPO PPOPolicy (algorithms/mappo/ppo_policy.py) on the device: DevicePolicy's actor for observations up to 640 wide, and a
+    critic on ``cent_obs`` (``share_obs``, up to 640 wide). ``get_actions`` / ``get_values`` take explicit ``cent_obs`` rows;
+    ``get_actions_into_env`` / ``get_values_from_env`` let the critic read each env's observation block in the env's device buffer
+    (``cent_obs_space`` must then be ``num_agents * obs_dim`` wide), so ``share_obs`` is never built. ``act`` / ``act_into_env``, the
+    weight loads and ``packed`` are DevicePolicy's. Blobs: ``blob_keys``; the critic's ``base.mlp.fc.0.weight`` is [128, cent_obs_dim]."""
+
+    def __init__(self, obs_space, cent_obs_space, act_space, args, device_id=0, precision="fast", seed=0, critic=True):
+        self.lib = load_library()
+        self.mcfg = make_mappo_config(obs_space, cent_obs_space, act_space, args, precision, critic)
+        self.cfg = self.mcfg.base
+        self.actor_floats, self.critic_floats = check_mappo_config(self.mcfg, self.lib)
+        self.obs_dim = int(self.cfg.obs_dim)
+        self.cent_obs_dim = int(self.mcfg.cent_obs_dim)
+        self.n_heads = int(self.cfg.n_cat + self.cfg.n_shoot)
+        self.has_critic = bool(critic)
+        self.device_id = int(device_id)
+        self.precision = precision
+        self.seed = int(seed)
+        self.counter = 0
+        h = C.c_void_p()
+        self.lib.check(self.lib.ac_policy_mappo_create(self.device_id, C.byref(self.mcfg), C.byref(h)), "ac_policy_mappo_create")
+        self._h = h
+
+    def _launch(self, rows, obs, h_a, h_c, masks, deterministic, values, actions, logp, h_a_out, h_c_out, counter, cin=None,
+                mode=AC_CENT_EXPLICIT):
+        import torch
+        ptr = lambda t: None if t is None else t.data_ptr()
+        stream = torch.cuda.current_stream(torch.device("cuda", self.device_id)).cuda_stream
+        if counter is None:
+            counter = self.counter
+            self.counter += 1
+        self.lib.check(self.lib.ac_policy_get_actions_mappo(
+            self._h, stream, C.byref(rows), ptr(obs), ptr(cin), int(mode), ptr(h_a), ptr(h_c), ptr(masks), int(bool(deterministic)),
+            C.c_uint64(self.seed & (2 ** 64 - 1)), C.c_uint64(int(counter) & (2 ** 64 - 1)), ptr(values), ptr(actions), ptr(logp),
+            ptr(h_a_out), ptr(h_c_out)), "ac_policy_get_actions_mappo")
+        return counter
+
+    def get_actions(self, cent_obs, obs, rnn_states_actor, rnn_states_critic, masks, deterministic=False, counter=None):
+        """values [N, 1], actions [N, n_heads] (float32), action_log_probs [N, 1], rnn_states_actor / _critic [N, 1, 128] -- like the
+        MAPPO PPOPolicy.get_actions. torch in, torch out (on torch's current stream); numpy in, numpy out."""
+        import torch
+        if not self.has_critic:
+            raise RuntimeError("get_actions: the policy was created without a critic (use act)")
+        o, was_np = self._tensor(obs, (self.obs_dim,))
+        n = o.shape[0]
+        co, _ = self._tensor(cent_obs, (self.cent_obs_dim,))
+        ha, _ = self._tensor(rnn_states_actor, (HID,))
+        hc, _ = self._tensor(rnn_states_critic, (HID,))
+        m, _ = self._tensor(masks, ())
+        if co.shape[0] != n or ha.shape[0] != n or hc.shape[0] != n or m.shape[0] != n:
+            raise ValueError("get_actions: cent_obs, obs, rnn states and masks disagree on the number of rows")
+        dev = o.device
+        values = torch.empty((n, 1), device=dev)
+        actions = torch.empty((n, self.n_heads), device=dev)
+        logp = torch.empty((n, 1), device=dev)
+        ha_out = torch.empty((n, 1, HID), device=dev)
+        hc_out = torch.empty((n, 1, HID), device=dev)
+        self.last_counter = self._launch(AcPolicyRows(n, 0, 0, 0, self.n_heads), o, ha, hc, m, deterministic, values, actions, logp,
+                                         ha_out, hc_out, counter, cin=co)
+        self._keep_call = (o, co, ha, hc, m)
+        out = (values, actions, logp, ha_out, hc_out)
+        if was_np:
+            torch.cuda.current_stream(dev).synchronize()
+            return tuple(t.cpu().numpy() for t in out)
+        return out
+
+    def get_values(self, cent_obs, rnn_states_critic, masks):
+        """values [N, 1] -- the MAPPO PPOPolicy.get_values (critic workgroups only; bit-identical to get_actions' values)."""
+        co, was_np = self._tensor(cent_obs, (self.cent_obs_dim,))
+        return self._values(AcPolicyRows(co.shape[0], 0, 0, 0, self.n_heads), co, AC_CENT_EXPLICIT, rnn_states_critic, masks, was_np)
+
+    def _env_rows(self, env, agents, what):
+        E, A = env.num_envs, env.num_agents
+        a0, a1, step = (agents or slice(0, A)).indices(A)
+        if step != 1 or a1 <= a0:
+            raise ValueError(f"{what}: agents must be a contiguous, non-empty slice")
+        if env.obs_dim != self.obs_dim or env.act_dim < self.n_heads:
+            raise ValueError(f"{what}: env obs_dim {env.obs_dim} / act_dim {env.act_dim} do not fit this policy")
+        if self.has_critic and self.cent_obs_dim != A * self.obs_dim:
+            raise UnsupportedPolicy(f"{what}: cent_obs_space is {self.cent_obs_dim} wide, the env share input is num_agents * obs_dim = "
+                                    f"{A} * {self.obs_dim} = {A * self.obs_dim}")
+        return E * (a1 - a0), AcPolicyRows(E * (a1 - a0), a1 - a0, A, a0, env.act_dim)
+
+    @staticmethod
+    def _check_rows(n, what, **ts):
+        for name, t in ts.items():
+            if t.numel() != n * (HID if name.startswith("rnn") else 1) or not t.is_contiguous():
+                raise ValueError(f"{what}: {name} must be contiguous with {n} rows (E * (a1 - a0), in (env, agent) order)")
+
+    def get_actions_into_env(self, env, rnn_states_actor, rnn_states_critic, masks, agents=None, deterministic=False, counter=None,
+                             rnn_states_actor_out=None, rnn_states_critic_out=None):
+        """get_actions for agents ``agents`` (a slice [a0, a1) of every env) of a HipShareVecEnv on the device: the actor reads their rows
+        of the env's obs buffer, the critic each env's whole observation block (share_obs, never built), and the actions go straight
+        into the env's device action buffer. States / masks: contiguous torch tensors [E * (a1 - a0), 1, 128] / [E * (a1 - a0), 1];
+        the new states go to the ``*_out`` tensors (default: in place). Returns (values, log-probs, rnn_states_actor, rnn_states_critic)."""
+        import torch
+        if not self.has_critic:
+            raise RuntimeError("get_actions_into_env: the policy was created without a critic (use act_into_env)")
+        n, rows = self._env_rows(env, agents, "get_actions_into_env")
+        self._check_rows(n, "get_actions_into_env", rnn_states_actor=rnn_states_actor, rnn_states_critic=rnn_states_critic, masks=masks)
+        act, obs, _, _, _ = env.device_tensors()
+        ha_out = rnn_states_actor if rnn_states_actor_out is None else rnn_states_actor_out
+        hc_out = rnn_states_critic if rnn_states_critic_out is None else rnn_states_critic_out
+        values = torch.empty((n, 1), device=obs.device)
+        logp = torch.empty((n, 1), device=obs.device)
+        self.last_counter = self._launch(rows, obs, rnn_states_actor, rnn_states_critic, masks, deterministic, values, act, logp, ha_out,
+                                         hc_out, counter, mode=AC_CENT_ENV_SHARE)
+        return values, logp, ha_out, hc_out
+
+    def get_values_from_env(self, env, rnn_states_critic, masks, agents=None):
+        """values [E * (a1 - a0), 1] of agents ``agents`` with each env's observation block as the critic input (the runner's compute()
+        on the last observations)."""
+        n, rows = self._env_rows(env, agents, "get_values_from_env")
+        self._check_rows(n, "get_values_from_env", rnn_states_critic=rnn_states_critic, masks=masks)
+        _, obs, _, _, _ = env.device_tensors()
+        return self._values(rows, obs, AC_CENT_ENV_SHARE, rnn_states_critic, masks, False)

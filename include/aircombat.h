@@ -311,6 +311,28 @@ int ac_policy_packed(ac_policy_t* h, int32_t net, void** d_ptr, int64_t* floats)
 int ac_policy_get_actions(ac_policy_t* h, void* stream, const ac_policy_rows_t* rows, const float* d_obs, const float* d_rnn_actor,
                           const float* d_rnn_critic, const float* d_masks, int32_t deterministic, uint64_t seed, uint64_t counter,
                           float* d_values, float* d_actions, float* d_logp, float* d_rnn_actor_out, float* d_rnn_critic_out);
+/* ---- the MAPPO rollout policy on the device (algorithms/mappo/ppo_policy.py of the reference; DESIGN.md, "The PPO rollout policy"): the
+ * same actor and heads, input widths up to 640 for both networks, and a centralised critic whose input is cent_obs_dim wide. Its blobs
+ * are the PPO ones with the critic's feature_norm / base.mlp.fc.0.weight [128, cent_obs_dim]. Loads, ac_policy_packed and
+ * ac_policy_destroy take both kinds of handle. */
+typedef struct {
+  ac_policy_config_t base;              /* base.obs_dim: 1 .. 640 */
+  int32_t cent_obs_dim;                 /* 1 .. 640 (the critic's input width; checked when base.has_critic) */
+} ac_policy_mappo_config_t;
+#define AC_CENT_EXPLICIT 0              /* critic row r reads d_cent_obs + r * cent_obs_dim */
+#define AC_CENT_ENV_SHARE 1             /* critic row r of an agent-range call reads env r / na's whole obs block (cent_obs_dim = A * obs_dim) */
+int ac_policy_mappo_blob_floats(const ac_policy_mappo_config_t* cfg, int64_t* actor_floats, int64_t* critic_floats);
+int ac_policy_mappo_create(int32_t device_id, const ac_policy_mappo_config_t* cfg, ac_policy_t** out);
+/* ac_policy_get_actions for a MAPPO handle: the actor reads d_obs (rows as there), the critic reads cent_mode's input (d_cent_obs is
+ * unused with AC_CENT_ENV_SHARE). The critic's three pointers all NULL = actor only. */
+int ac_policy_get_actions_mappo(ac_policy_t* h, void* stream, const ac_policy_rows_t* rows, const float* d_obs, const float* d_cent_obs,
+                                int32_t cent_mode, const float* d_rnn_actor, const float* d_rnn_critic, const float* d_masks,
+                                int32_t deterministic, uint64_t seed, uint64_t counter, float* d_values, float* d_actions, float* d_logp,
+                                float* d_rnn_actor_out, float* d_rnn_critic_out);
+/* the critic alone (get_values; values [n] and its new state): d_in is the obs rows of a PPO handle (AC_CENT_EXPLICIT only), or
+ * cent_mode's input of a MAPPO handle (the obs buffer with AC_CENT_ENV_SHARE). Bit-identical to the values of a get_actions call. */
+int ac_policy_get_values(ac_policy_t* h, void* stream, const ac_policy_rows_t* rows, const float* d_in, int32_t cent_mode,
+                         const float* d_rnn_critic, const float* d_masks, float* d_values, float* d_rnn_critic_out);
 /* the draws of rows row0 .. row0 + nrows - 1, one head, on the host: uniform on [0, 1) in steps of 2^-24 */
 int ac_policy_draw_host(uint64_t seed, uint64_t counter, int64_t row0, int64_t nrows, int32_t head, float* out);
 

@@ -1,0 +1,90 @@
+"""The MAPPO golden cases (tests/golden/make_mappo_golden.py, from the reference's algorithms/mappo actor / critic) and their loader.
+
+The MAPPO actor is the PPO one and its critic is the PPO critic on ``cent_obs`` (every agent's observation of the env, concatenated),
+so the float64 restatement is policy_util's ``actor`` / ``critic``. The fixtures store the observations grouped by env ([E, A, D]),
+``cent_obs`` is derived from them, and the hashed weights / GRU inputs are regenerated here (only case d's actor, the shipped
+4v4_actor.pt, is stored)."""
+import os
+import types
+
+import numpy as np
+
+import policy_util as U
+
+GOLDEN_DIR = U.GOLDEN_DIR
+# tag: (obs_dim, cent_obs_dim, agents per env, nvec, n_shoot, use_feature_normalization, use_prior)
+CASES = {
+    "a": (39, 156, 4, [3, 5, 3], 4, False, True),        # scenario2_nvn (2v2)
+    "b": (65, 520, 8, [3, 5, 3], 4, True, True),         # scenario3 RWR (4v4)
+    "c": (51, 408, 8, [41, 41, 41, 30], 0, False, False),   # MultipleCombat 4v4
+    "d": (21, 168, 8, [3, 5, 3], 4, False, True),        # legacy 4v4 (scenario3): the shipped 4v4_actor.pt
+}
+FILES = {t: f"mappo_{t}.npz" for t in CASES}
+SEED_WEIGHTS = {"a": 201, "b": 202, "c": 203, "d": 204}
+
+
+def seeded_state_dicts(tag):
+    """(actor state_dict or None for case d, critic state_dict) from policy_util's hash: the actor of obs_dim (plus its munition heads
+    act.action_outs.{n_cat + s}.net, Linear(128, 2)), the critic of cent_obs_dim."""
+    obs_dim, cent, _, nvec, n_shoot, fn, _ = CASES[tag]
+    seed = SEED_WEIGHTS[tag]
+    critic = U.seeded_state_dicts(cent, nvec, fn, seed=seed)[1]
+    if tag == "d":
+        return None, critic
+    actor = U.seeded_state_dicts(obs_dim, nvec, fn, seed=seed)[0]
+    b = np.float32(1.0 / np.sqrt(128))
+    for s in range(n_shoot):
+        k = len(nvec) + s
+        actor[f"act.action_outs.{k}.net.weight"] = (U.hashed(seed * 1000 + 300 + s, 2 * 128) * b).reshape(2, 128)
+        actor[f"act.action_outs.{k}.net.bias"] = U.hashed(seed * 1000 + 400 + s, 2) * b
+    return actor, critic
+
+
+def golden_case(tag):
+    """One case: the stored arrays (obs flattened to [N, obs_dim], ``obs_env`` [E, A, obs_dim] as stored), ``cent_obs`` [N, cent],
+    the hashed GRU-state inputs, ``sd`` / ``critic_sd``."""
+    z = np.load(os.path.join(GOLDEN_DIR, FILES[tag]))
+    g = {k: z[k] for k in z.files if "/" not in k}
+    obs_dim, cent, A = CASES[tag][:3]
+    E = g["obs"].shape[0]
+    g["obs_env"] = g["obs"]
+    g["obs"] = g["obs_env"].reshape(E * A, obs_dim)
+    g["cent_obs"] = cent_obs(g["obs_env"])
+    n = E * A
+    g["rnn_states"] = U.hashed_states(U.SEED_RNN, n)
+    g["rnn_states_critic"] = U.hashed_states(U.SEED_RNN_CRITIC, n)
+    g["masks"] = g["masks"].astype(np.float32)
+    g["actions"] = g["actions"].astype(np.float64)
+    g["sd"], g["critic_sd"] = seeded_state_dicts(tag)
+    if g["sd"] is None:
+        g["sd"] = {k[3:]: z[k] for k in z.files if k.startswith("sd/")}
+    return g
+
+
+def cent_obs(obs_env):
+    """share_obs of an [E, A, D] observation block: row (e, a) is env e's observations concatenated (HipShareVecEnv._share)."""
+    E, A, D = obs_env.shape
+    return np.ascontiguousarray(np.broadcast_to(obs_env.reshape(E, 1, A * D), (E, A, A * D)).reshape(E * A, A * D))
+
+
+def spaces(tag):
+    """(obs_space, cent_obs_space, act_space) with the env's stand-in space classes."""
+    from importlib import import_module
+    ve = import_module("aircombat-selfplay_amd.vec_env")
+    obs_dim, cent, _, nvec, n_shoot = CASES[tag][:5]
+    act = ve._Tuple([ve._MultiDiscrete(nvec), ve._MultiDiscrete([2] * 4)]) if n_shoot else ve._MultiDiscrete(nvec)
+    return ve._Box(-10, 10, (obs_dim,)), ve._Box(-10, 10, (cent,)), act
+
+
+def args(tag):
+    fn, prior = CASES[tag][5:7]
+    return types.SimpleNamespace(hidden_size="128 128", act_hidden_size="128 128", recurrent_hidden_size=128, recurrent_hidden_layers=1,
+                                 activation_id=1, use_feature_normalization=fn, use_prior=prior, use_recurrent_policy=True)
+
+
+def restate(g, tag):
+    """The float64 restatement of the case: actor outputs and critic outputs in one dict."""
+    obs_dim, cent, A, nvec, n_shoot, fn, _ = CASES[tag]
+    out = U.actor(g["sd"], g["obs"], g["rnn_states"], g["masks"], nvec, n_shoot, fn)
+    out.update(U.critic(g["critic_sd"], g["cent_obs"], g["rnn_states_critic"], g["masks"], fn))
+    return out
