@@ -11,10 +11,10 @@ from .config import config_from_yaml, default_config, default_nvn_config, TASK_I
 from .vec_env import HipVecEnv, HipShareVecEnv, MultiDeviceVecEnv, make_env, controller_forward  # noqa: F401
 from .rollout_buffer import DeviceReplayBuffer, DeviceSharedReplayBuffer  # noqa: F401
 from .snapshot import EnvSnapshot, MultiSnapshot, SnapshotMismatch  # noqa: F401
-from .policy import DevicePolicy, DeviceMAPPOPolicy, UnsupportedPolicy  # noqa: F401
+from .policy import DevicePolicy, DeviceMAPPOPolicy, DevicePolicyPool, UnsupportedPolicy  # noqa: F401
 from . import sharding  # noqa: F401
 
 __all__ = ["AcConfig", "AcInitState", "Lib", "load_library", "library_path", "HipExtensionMissing",
            "config_from_yaml", "default_config", "default_nvn_config", "TASK_IDS", "HipVecEnv", "HipShareVecEnv", "MultiDeviceVecEnv", "make_env", "controller_forward",
            "DeviceReplayBuffer", "DeviceSharedReplayBuffer", "EnvSnapshot", "MultiSnapshot", "SnapshotMismatch",
-           "DevicePolicy", "DeviceMAPPOPolicy", "UnsupportedPolicy"]
+           "DevicePolicy", "DeviceMAPPOPolicy", "DevicePolicyPool", "UnsupportedPolicy"]

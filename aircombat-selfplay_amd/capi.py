@@ -15,6 +15,7 @@ AC_TASK_SCENARIO1, AC_TASK_SCENARIO_NVN, AC_TASK_WVR, AC_TASK_MANEUVER = 5, 6, 7
 AC_ALIVE, AC_CRASH, AC_SHOTDOWN = 0, 1, 2
 AC_CTL_FAST, AC_CTL_FP32 = 0, 1   # AcConfig.controller_precision: the low-level controller's arithmetic
 AC_CENT_EXPLICIT, AC_CENT_ENV_SHARE = 0, 1   # the MAPPO critic's input: explicit cent_obs rows, or each env's obs block (include/aircombat.h)
+AC_POOL_PPO, AC_POOL_MAPPO = 0, 1   # the form of a DevicePolicyPool's members
 
 
 class HipExtensionMissing(RuntimeError):
@@ -144,6 +145,21 @@ SIGNATURES = {
     "ac_policy_mappo_create": (C.c_int, [C.c_int32, _p, C.POINTER(_p)]),
     "ac_policy_get_actions_mappo": (C.c_int, [_p, _p, _p, _p, _p, C.c_int32, _p, _p, _p, C.c_int32, C.c_uint64, C.c_uint64, _p, _p, _p, _p, _p]),
     "ac_policy_get_values": (C.c_int, [_p, _p, _p, _p, C.c_int32, _p, _p, _p, _p]),
+    "ac_policy_pool_member_floats": (C.c_int, [_p, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "ac_policy_pool_compatible": (C.c_int, [_p, C.c_int32, _p, C.c_int32]),
+    "ac_policy_pool_create": (C.c_int, [C.c_int32, _p, C.c_int32, C.c_int32, C.POINTER(_p)]),
+    "ac_policy_pool_destroy": (C.c_int, [_p]),
+    "ac_policy_pool_load": (C.c_int, [_p, C.c_int32, _p, C.c_int64]),
+    "ac_policy_pool_load_device": (C.c_int, [_p, _p, C.c_int32, _p, C.c_int64]),
+    "ac_policy_pool_load_refused": (C.c_int, [_p, _p, C.POINTER(C.c_int32)]),
+    "ac_policy_pool_copy_from": (C.c_int, [_p, _p, C.c_int32, _p]),
+    "ac_policy_pool_packed": (C.c_int, [_p, C.c_int32, C.POINTER(_p), C.POINTER(C.c_int64)]),
+    "ac_policy_pool_assign": (C.c_int, [_p, _p, _p, C.c_int64, C.c_int32]),
+    "ac_policy_pool_check": (C.c_int, [_p, _p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "ac_policy_pool_plan_host": (C.c_int, [_p, C.c_int64, C.c_int32, C.c_int32, _p, _p, _p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "ac_policy_pool_max_tiles": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
+    "ac_policy_pool_set_tile_order": (C.c_int, [_p, C.c_int32]),
+    "ac_policy_pool_act": (C.c_int, [_p, _p, _p, _p, _p, _p, C.c_int32, C.c_uint64, C.c_uint64, _p, _p, _p]),
     "ac_last_error": (C.c_char_p, []),
     "ac_version": (C.c_char_p, []),
     # include/aircombat_buffer.h

@@ -170,6 +170,24 @@ __host__ __device__ inline unsigned policy_pack_wide(const float* src, const Pac
   memcpy(&b, &v, 4);
   return b;
 }
+// The pool form (policy_pool_kernel, policy_pool_wide_kernel; csrc/policy_pool.hpp): one workgroup per tile of the plan, a tile being
+// 1 .. 32 call rows of one member. Call row order[p] for p in [p0, p1); every row keeps its own positions in the buffers (the row
+// indirection), and its draws are keyed by its call row as in the plain call.
+struct Pool {
+  const float* W0;             // member m's packed actor at W0 + m * stride
+  long long stride;
+  const int4* tiles;           // {member, p0, p1, 0}
+  const int* order;            // the call rows, stably sorted by member
+  const int* ntiles;           // tiles in the plan: workgroups past it exit
+  int xcd;                     // 1: the tiles dealt so that a member's tiles share blockIdx.x % 8 (one XCD's L2; speed only)
+};
+// the tile of workgroup b (nt = none): the plain order, or the tile list cut into eight contiguous runs, run x taken by the workgroups
+// b = x (mod 8) in order
+__device__ __forceinline__ int pool_tile(int b, int nt, int xcd) {
+  if (!xcd) return b;
+  const int x = b & 7, j = b >> 3, q = nt >> 3, r = nt & 7;
+  return j < q + (x < r ? 1 : 0) ? x * q + min(x, r) + j : nt;
+}
 __device__ __forceinline__ float softplus_t(float x) { return x > 20.0f ? x : log1pf(__expf(x)); }   // torch.nn.Softplus (threshold 20)
 
 template <int NP>
@@ -192,9 +210,11 @@ __device__ __forceinline__ void relu_out(float* stg, const ctl8::floatx4 (&acc)[
 // The PPO form's kernel (policy_kernel, at the end) is kept as it was written: the same body routed through this template compiles to a
 // different schedule (224 -> 222 VGPRs for NP = 3), and its figures and results are pinned. This template is the body of the new kernels:
 // WIDE = the wide input layer and the critic input of pol::Wide (policy_wide_kernel), else the PPO form's K = 32 one; VALUES = the PPO
-// form's critic-only launch (policy_values_kernel; the wide form's is wx.net0). Past layer 1 it is policy_kernel's code.
-template <int NP, bool WIDE, bool VALUES>
-__device__ __forceinline__ void policy_body(const pol::Args& a, const pol::Wide& wx) {
+// form's critic-only launch (policy_values_kernel; the wide form's is wx.net0); POOL = the actor of the plan's tile's member for the rows
+// px.order lists (policy_pool_kernel / policy_pool_wide_kernel; the other instances compile as without it). Past layer 1 it is
+// policy_kernel's code.
+template <int NP, bool WIDE, bool VALUES, bool POOL = false>
+__device__ __forceinline__ void policy_body(const pol::Args& a, const pol::Wide& wx, const pol::Pool& px = pol::Pool{}) {
   using namespace ctl8;
   using namespace pol;
   using ctl::sigmoid_f; using ctl::tanh_f;
@@ -213,12 +233,20 @@ __device__ __forceinline__ void policy_body(const pol::Args& a, const pol::Wide&
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int net = WIDE ? blockIdx.y + wx.net0 : (VALUES ? 1 : blockIdx.y);   // 0 actor, 1 critic
+  const int net = POOL ? 0 : (WIDE ? blockIdx.y + wx.net0 : (VALUES ? 1 : blockIdx.y));   // 0 actor, 1 critic
   const int i0 = blockIdx.x * R;
-  const float* __restrict__ W = a.W[net];
+  int4 tl = make_int4(0, 0, 0, 0);   // the pool form's tile: {member, p0, p1}
+  if constexpr (POOL) {
+    const int nt = *px.ntiles;
+    const int t = pol::pool_tile(blockIdx.x, nt, px.xcd);
+    if (t >= nt) return;
+    tl = px.tiles[t];
+  }
+  const float* __restrict__ W = POOL ? px.W0 + tl.x * px.stride : a.W[net];
   const int col = lane & 15;
   const int srow = tid % R, spart = tid / R;   // staging: thread = (row, 8-feature part)
-  const int sn = min(i0 + srow, a.n - 1);
+  // (a padding slot of a pool tile reads the member's last row)
+  const int sn = POOL ? px.order[min(tl.y + srow, tl.z - 1)] : min(i0 + srow, a.n - 1);
   const long long senv = (long long)(sn / a.na) * a.A + a.a0 + sn % a.na;
 
   // ---- stage: the observation (LayerNorm'd when use_feature_normalization), the masked GRU state, the shoot prior
@@ -398,8 +426,8 @@ __device__ __forceinline__ void policy_body(const pol::Args& a, const pol::Wide&
   }
   __syncthreads();
   {   // the new state goes out row-contiguous; every row of this workgroup was read into LDS above (in-place states are fine)
-    const int n = i0 + srow;
-    if (n < a.n) {
+    const int n = POOL ? sn : i0 + srow;
+    if (POOL ? tl.y + srow < tl.z : n < a.n) {
       float4* dst = reinterpret_cast<float4*>(a.h_out[net] + (size_t)n * HID + 8 * spart);
       dst[0] = *reinterpret_cast<const float4*>(stg + srow * RS + 8 * spart);
       dst[1] = *reinterpret_cast<const float4*>(stg + srow * RS + 8 * spart + 4);
@@ -427,7 +455,7 @@ __device__ __forceinline__ void policy_body(const pol::Args& a, const pol::Wide&
   __syncthreads();
   layer_norm_planes<MTL, NP>(stg, PA, W + L::G4, W + L::BE4, tid);
 
-  if (net == 1) {   // ---- the critic: value_out = column 0 of tile 0 (wave 0)
+  if (!POOL && net == 1) {   // ---- the critic: value_out = column 0 of tile 0 (wave 0)
     if (w == 0) {
       prefetch_bt<HID, NP>(W + L::WO, lane, bt);
       floatx4 acc[MTL];
@@ -466,7 +494,7 @@ __device__ __forceinline__ void policy_body(const pol::Args& a, const pol::Wide&
   // ---- sampling: thread = (head, row); log-probs of the chosen actions from an fp32 log-softmax (max first)
   const int nh = a.n_cat + a.n_shoot;
   if (tid < nh * R) {
-    const int head = tid / R, row = tid % R, n = i0 + row;
+    const int head = tid / R, row = tid % R, n = POOL ? px.order[min(tl.y + row, tl.z - 1)] : i0 + row;
     const float u = a.deterministic ? 0.0f : pol::policy_uniform(a.seed, a.counter, n, head);
     float act, lp;
     if (head < a.n_cat) {
@@ -509,16 +537,16 @@ __device__ __forceinline__ void policy_body(const pol::Args& a, const pol::Wide&
       lp = fire ? __logf(pc) : log1pf(-pc);
     }
     lpart[row][head] = lp;
-    if (n < a.n) {
+    if (POOL ? tl.y + row < tl.z : n < a.n) {
       const long long env = (long long)(n / a.na) * a.A + a.a0 + n % a.na;
       a.actions[env * a.act_stride + head] = act;
     }
   }
   __syncthreads();
-  if (tid < R && i0 + tid < a.n) {   // ACTLayer.forward: the heads' log-probs summed in head order
+  if (tid < R && (POOL ? tl.y + tid < tl.z : i0 + tid < a.n)) {   // ACTLayer.forward: the heads' log-probs summed in head order
     float s = 0.0f;
     for (int h = 0; h < nh; ++h) s += lpart[tid][h];
-    a.logp[i0 + tid] = s;
+    a.logp[POOL ? px.order[tl.y + tid] : i0 + tid] = s;
   }
 }
 
@@ -527,6 +555,12 @@ __global__ __launch_bounds__(512) void policy_values_kernel(pol::Args a) { polic
 // the MAPPO policy (wide inputs, a centralised critic): csrc/policy_host.hpp, ac_policy_get_actions_mappo / ac_policy_get_values
 template <int NP>
 __global__ __launch_bounds__(512) void policy_wide_kernel(pol::Args a, pol::Wide x) { policy_body<NP, true, false>(a, x); }
+
+// the pool of actors (csrc/policy_pool.hpp, ac_policy_pool_act): grid = the plan's tiles (or a bound, past which workgroups exit)
+template <int NP>
+__global__ __launch_bounds__(512) void policy_pool_kernel(pol::Args a, pol::Pool p) { policy_body<NP, false, false, true>(a, pol::Wide{}, p); }
+template <int NP>
+__global__ __launch_bounds__(512) void policy_pool_wide_kernel(pol::Args a, pol::Wide x, pol::Pool p) { policy_body<NP, true, false, true>(a, x, p); }
 
 template <int NP>
 __global__ __launch_bounds__(512) void policy_kernel(pol::Args a) {

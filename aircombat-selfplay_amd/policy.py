@@ -12,12 +12,15 @@ Weight blobs (fp32) follow the state_dict tensors in the order ``blob_keys`` lis
 
 ``DeviceMAPPOPolicy`` is the MAPPO form (algorithms/mappo/ppo_policy.py): the same actor, with input widths up to 640, and a critic on
 ``cent_obs`` / ``share_obs`` (up to 640 wide), fed either explicit rows or, straight from an env, each env's whole observation block.
+
+``DevicePolicyPool`` holds many actors of either form (the self-play opponents) and acts for every env with its assigned member in one
+launch.
 """
 import ctypes as C
 
 import numpy as np
 
-from .capi import load_library, AC_CTL_FAST, AC_CTL_FP32, AC_CENT_EXPLICIT, AC_CENT_ENV_SHARE
+from .capi import load_library, AC_CTL_FAST, AC_CTL_FP32, AC_CENT_EXPLICIT, AC_CENT_ENV_SHARE, AC_POOL_PPO, AC_POOL_MAPPO
 
 HID = 128
 
@@ -504,3 +507,224 @@ class DeviceMAPPOPolicy(DevicePolicy):
         self._check_rows(n, "get_values_from_env", rnn_states_critic=rnn_states_critic, masks=masks)
         _, obs, _, _, _ = env.device_tensors()
         return self._values(rows, obs, AC_CENT_ENV_SHARE, rnn_states_critic, masks, False)
+
+
+class DevicePolicyPool:
+    """A pool of ``capacity`` actors on the device, the self-play opponents of the reference's runners, acted for in one launch
+    (csrc/policy_pool.hpp). Every member is packed as ``DevicePolicy`` (``form="ppo"``) or ``DeviceMAPPOPolicy`` (``form="mappo"``)
+    packs its actor, with one precision for the whole pool. ``assign`` maps each env to a member (-1: not acted for); ``act_into_env`` /
+    ``act`` then act for every assigned row with its member's weights, with ``DevicePolicy``'s sampling: draws keyed by (seed, counter,
+    row of the call, head), so each row's output is the one a DevicePolicy holding that member would give in the same call.
+
+    The host-side choice of opponents (``selfplay_algo.choose``, the ELO update) stays the reference's: the runner maps its policy-pool
+    keys to member indices, loads them, and calls ``assign``. Assign after loading: a member's load state is
+    read when the assignment is planned."""
+
+    def __init__(self, obs_space, act_space, args, capacity, form="ppo", precision="fast", seed=0, device_id=0):
+        if form not in ("ppo", "mappo"):
+            raise ValueError("form is 'ppo' or 'mappo'")
+        self.lib = load_library()
+        self.cfg = make_config(obs_space, act_space, args, precision, has_critic=False)
+        self.form, self._form = form, (AC_POOL_MAPPO if form == "mappo" else AC_POOL_PPO)
+        self.capacity = int(capacity)
+        ns, npk = C.c_int64(), C.c_int64()
+        if self.lib.ac_policy_pool_member_floats(C.byref(self.cfg), self._form, self.capacity, C.byref(ns), C.byref(npk)) != 0:
+            raise UnsupportedPolicy(self.lib.last_error())
+        self.actor_floats, self.packed_floats = int(ns.value), int(npk.value)
+        self.obs_dim = int(self.cfg.obs_dim)
+        self.n_heads = int(self.cfg.n_cat + self.cfg.n_shoot)
+        self.device_id = int(device_id)
+        self.precision = precision
+        self.seed = int(seed)
+        self.counter = 0
+        self._na = 1        # rows per env of the plan (the agent count of the calls)
+        self._members = None
+        h = C.c_void_p()
+        self.lib.check(self.lib.ac_policy_pool_create(self.device_id, C.byref(self.cfg), self._form, self.capacity, C.byref(h)),
+                       "ac_policy_pool_create")
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self.lib.ac_policy_pool_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _stream(self):
+        import torch
+        return torch.cuda.current_stream(torch.device("cuda", self.device_id)).cuda_stream
+
+    def _member(self, member):
+        m = int(member)
+        if not 0 <= m < self.capacity:
+            raise ValueError(f"member {m} out of range (capacity {self.capacity})")
+        return m
+
+    # ---- members
+    def load_state_dict(self, member, actor_sd):
+        """Member ``member`` from the reference's actor state_dict (or the path of an ``actor_{episode}.pt``), host path."""
+        self.load_blob(member, blob_from_state_dict(self.cfg, _load_sd(actor_sd)))
+
+    def load_blob(self, member, actor):
+        a = np.ascontiguousarray(actor, dtype=np.float32)
+        self.lib.check(self.lib.ac_policy_pool_load(self._h, self._member(member), a.ctypes.data, a.size), "ac_policy_pool_load")
+
+    def load_from_torch(self, member, actor_module, check=True):
+        """Member ``member`` from a torch actor module (or state_dict) on this GPU, packed on the device on torch's stream. A refused load
+        (a non-finite weight; |w| >= 65504 in the fast form) keeps the member's previous weights; with ``check`` it raises."""
+        import torch
+        sd = actor_module.state_dict() if hasattr(actor_module, "state_dict") else actor_module
+        a = torch.cat([sd[k].detach().reshape(-1).to(torch.float32) for k in blob_keys(self.cfg)[0]]).contiguous()
+        stream = torch.cuda.current_stream(a.device).cuda_stream
+        self.lib.check(self.lib.ac_policy_pool_load_device(self._h, stream, self._member(member), a.data_ptr(), a.numel()),
+                       "ac_policy_pool_load_device")
+        self._keep = a   # alive until the packing kernel has run
+        if check:
+            r = C.c_int32()
+            self.lib.check(self.lib.ac_policy_pool_load_refused(self._h, stream, C.byref(r)), "ac_policy_pool_load_refused")
+            if r.value:
+                raise ValueError("load_from_torch: weights refused (non-finite, or |w| >= 65504 in the fast form); previous weights kept")
+
+    def copy_from(self, member, device_policy):
+        """Member ``member`` := ``device_policy``'s packed actor (a DevicePolicy for the ppo form, a DeviceMAPPOPolicy for the mappo form,
+        same configuration and precision), device to device on torch's stream: the learner's actor joins the pool with no file."""
+        self.lib.check(self.lib.ac_policy_pool_copy_from(self._h, self._stream(), self._member(member), device_policy._h),
+                       "ac_policy_pool_copy_from")
+
+    def packed(self, member):
+        """Member ``member``'s packed weights as a torch uint8 tensor copy (test aid)."""
+        import torch
+        p, n = C.c_void_p(), C.c_int64()
+        self.lib.check(self.lib.ac_policy_pool_packed(self._h, self._member(member), C.byref(p), C.byref(n)), "ac_policy_pool_packed")
+        holder = type("_Packed", (), {})()
+        holder.__cuda_array_interface__ = {"shape": (int(n.value) * 4,), "typestr": "|u1", "data": (p.value, False), "version": 2}
+        return torch.as_tensor(holder, device=f"cuda:{self.device_id}").clone()
+
+    def set_tile_order(self, xcd):
+        """Deal each member's tiles to workgroups that share one XCD (True, the default) or in member-major order (False); speed only."""
+        self.lib.check(self.lib.ac_policy_pool_set_tile_order(self._h, int(bool(xcd))), "ac_policy_pool_set_tile_order")
+
+    # ---- assignment
+    def assign(self, members, check=True, na=None):
+        """Env e's rows act with member ``members[e]`` (-1: not acted for, their outputs untouched); ``members``: numpy or a torch int
+        tensor of length E. Planned on the device on torch's stream and kept for every later call (``na``: rows per env of those calls,
+        default the last call's). With ``check``, one sync reads back the plan: a ValueError names the first env whose member is out of
+        range or not loaded, and the exact tile count becomes the act launch's grid."""
+        import torch
+        dev = torch.device("cuda", self.device_id)
+        if isinstance(members, torch.Tensor):
+            m = members.to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
+        else:
+            m = torch.as_tensor(np.ascontiguousarray(np.asarray(members).reshape(-1), dtype=np.int32)).to(dev)
+        if na is not None:
+            self._na = int(na)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        self.lib.check(self.lib.ac_policy_pool_assign(self._h, stream, m.data_ptr(), m.numel(), self._na), "ac_policy_pool_assign")
+        self._members = m   # alive until the copy has run
+        self.num_envs = int(m.numel())
+        if check:
+            bad, nt = C.c_int32(), C.c_int32()
+            self.lib.check(self.lib.ac_policy_pool_check(self._h, stream, C.byref(bad), C.byref(nt)), "ac_policy_pool_check")
+            self.num_tiles = int(nt.value)
+            if bad.value >= 0:
+                v = int(m[bad.value].item())
+                why = f"out of range (capacity {self.capacity})" if not 0 <= v < self.capacity else "not loaded"
+                raise ValueError(f"assign: env {bad.value} has member {v}, {why}")
+        return self
+
+    def assign_split(self, E, member_ids, check=True, na=None):
+        """The reference's split: ``np.array_split(np.arange(E), K)``, range k to ``member_ids[k]``."""
+        members = np.empty(int(E), dtype=np.int32)
+        for k, idx in enumerate(np.array_split(np.arange(int(E)), len(member_ids))):
+            members[idx] = int(member_ids[k])
+        return self.assign(members, check=check, na=na)
+
+    # ---- calls
+    def _launch(self, rows, obs, h, masks, deterministic, actions, logp, h_out, counter):
+        if counter is None:
+            counter = self.counter
+            self.counter += 1
+        self._na = int(rows.na) if rows.na > 0 else 1
+        self.lib.check(self.lib.ac_policy_pool_act(
+            self._h, self._stream(), C.byref(rows), obs.data_ptr(), h.data_ptr(), masks.data_ptr(), int(bool(deterministic)),
+            C.c_uint64(self.seed & (2 ** 64 - 1)), C.c_uint64(int(counter) & (2 ** 64 - 1)), actions.data_ptr(), logp.data_ptr(),
+            h_out.data_ptr()), "ac_policy_pool_act")
+        return counter
+
+    def act_into_env(self, env, rnn_states, masks, agents=None, deterministic=False, counter=None, rnn_states_out=None, logp_out=None):
+        """DevicePolicy.act_into_env for the pool: agents ``agents`` (default the second half, ``slice(A // 2, A)``, the opponents) of
+        every env, each env with its assigned member; the actions go straight into ``env``'s device action buffer. ``rnn_states`` /
+        ``masks``: contiguous [E * (a1 - a0), 1, 128] / [E * (a1 - a0), 1] torch tensors in (env, agent) order; the new states go to
+        ``rnn_states_out`` (default: in place). Returns (rnn_states_out, log-probs [E * (a1 - a0), 1]); the rows of unassigned envs are
+        not written in any of them (``logp_out`` may supply the log-prob tensor)."""
+        import torch
+        E, A = env.num_envs, env.num_agents
+        a0, a1, step = (agents or slice(A // 2, A)).indices(A)
+        if step != 1 or a1 <= a0:
+            raise ValueError("act_into_env: agents must be a contiguous, non-empty slice")
+        if env.obs_dim != self.obs_dim or env.act_dim < self.n_heads:
+            raise ValueError(f"act_into_env: env obs_dim {env.obs_dim} / act_dim {env.act_dim} do not fit this pool")
+        act, obs, _, _, _ = env.device_tensors()
+        n = E * (a1 - a0)
+        if rnn_states.numel() != n * HID or masks.numel() != n or not rnn_states.is_contiguous() or not masks.is_contiguous():
+            raise ValueError("act_into_env: rnn_states / masks must be contiguous [E * (a1 - a0), 1, 128] / [E * (a1 - a0), 1]")
+        out = rnn_states if rnn_states_out is None else rnn_states_out
+        logp = torch.empty((n, 1), device=obs.device) if logp_out is None else logp_out
+        self.last_counter = self._launch(AcPolicyRows(n, a1 - a0, A, a0, env.act_dim), obs, rnn_states, masks, deterministic, act, logp,
+                                         out, counter)
+        return out, logp
+
+    def act(self, obs, rnn_states, masks, deterministic=False, counter=None, return_log_probs=False):
+        """actions [N, n_heads], rnn_states [N, 1, 128] (with ``return_log_probs`` also the log-probs) for explicit rows, row e acting
+        with member ``members[e]`` of the assignment (one row per env). Unassigned rows come back zero. torch in, torch out (on torch's
+        current stream); numpy in, numpy out."""
+        import torch
+        dev = torch.device("cuda", self.device_id)
+        was_np = not isinstance(obs, torch.Tensor)
+        cv = lambda x, tail: torch.as_tensor(np.asarray(x, dtype=np.float32) if not isinstance(x, torch.Tensor) else x).to(
+            device=dev, dtype=torch.float32).reshape((-1,) + tail).contiguous()
+        o, h, m = cv(obs, (self.obs_dim,)), cv(rnn_states, (HID,)), cv(masks, ())
+        n = o.shape[0]
+        if h.shape[0] != n or m.shape[0] != n:
+            raise ValueError("act: obs, rnn states and masks disagree on the number of rows")
+        actions = torch.zeros((n, self.n_heads), device=dev)
+        logp = torch.zeros((n, 1), device=dev)
+        h_out = torch.zeros((n, 1, HID), device=dev)
+        self.last_counter = self._launch(AcPolicyRows(n, 0, 0, 0, self.n_heads), o, h, m, deterministic, actions, logp, h_out, counter)
+        self._keep_call = (o, h, m)
+        out = (actions, h_out, logp) if return_log_probs else (actions, h_out)
+        if was_np:
+            torch.cuda.current_stream(dev).synchronize()
+            return tuple(t.cpu().numpy() for t in out)
+        return out
+
+
+def plan_host(members, na, capacity, loaded=None, lib=None):
+    """The assignment's plan as the device builds it, on the host: (order [E * na] call rows by member, tiles [T, 3] {member, p0, p1} =
+    rows order[p0:p1], first bad env or -1)."""
+    lib = lib or load_library()
+    m = np.ascontiguousarray(np.asarray(members).reshape(-1), dtype=np.int32)
+    E = m.size
+    mt = C.c_int64()
+    lib.check(lib.ac_policy_pool_max_tiles(E, int(na), int(capacity), C.byref(mt)), "ac_policy_pool_max_tiles")
+    order = np.full(E * int(na), -1, dtype=np.int32)
+    tiles = np.zeros((max(int(mt.value), 1), 3), dtype=np.int32)
+    ld = None if loaded is None else np.ascontiguousarray(np.asarray(loaded).reshape(-1), dtype=np.int32)
+    if ld is not None and ld.size != int(capacity):
+        raise ValueError("plan_host: loaded must have capacity entries")
+    nt, bad = C.c_int32(), C.c_int32()
+    lib.check(lib.ac_policy_pool_plan_host(m.ctypes.data, E, int(na), int(capacity), None if ld is None else ld.ctypes.data, order.ctypes.data,
+                                           tiles.ctypes.data, C.byref(nt), C.byref(bad)), "ac_policy_pool_plan_host")
+    return order, tiles[:nt.value].copy(), int(bad.value)
+
+
+def pool_compatible(pool_cfg, pool_form, cfg, form, lib=None):
+    """None when a policy of (cfg, form) may be copied into a pool of (pool_cfg, pool_form) (forms "ppo" / "mappo"), else the reason."""
+    lib = lib or load_library()
+    f = lambda s: AC_POOL_MAPPO if s == "mappo" else AC_POOL_PPO
+    return None if lib.ac_policy_pool_compatible(C.byref(pool_cfg), f(pool_form), C.byref(cfg), f(form)) == 0 else lib.last_error()

@@ -336,6 +336,48 @@ int ac_policy_get_values(ac_policy_t* h, void* stream, const ac_policy_rows_t* r
 /* the draws of rows row0 .. row0 + nrows - 1, one head, on the host: uniform on [0, 1) in steps of 2^-24 */
 int ac_policy_draw_host(uint64_t seed, uint64_t counter, int64_t row0, int64_t nrows, int32_t head, float* out);
 
+/* ---- a pool of actors on the device (the self-play opponents; DESIGN.md, "The opponent pool"): `capacity` actors in one device array,
+ * each packed as a DevicePolicy (AC_POOL_PPO, obs_dim <= 32) or DeviceMAPPOPolicy (AC_POOL_MAPPO, obs_dim <= 640) packs its actor; one
+ * precision and one form for the whole pool. cfg is the policy's configuration (a MAPPO configuration's base); has_critic is ignored.
+ * An assignment maps each env to a member, and one launch acts for every assigned row with its member's weights. */
+typedef struct ac_policy_pool_s ac_policy_pool_t;
+#define AC_POOL_PPO 0
+#define AC_POOL_MAPPO 1
+/* no device needed: the refusals of ac_policy_pool_create, and the source / packed float count of one member */
+int ac_policy_pool_member_floats(const ac_policy_config_t* cfg, int32_t form, int32_t capacity, int64_t* src_floats, int64_t* packed_floats);
+/* 0 when a policy of (cfg, form) may be copied into a pool of (pool_cfg, pool_form); else -1, ac_last_error naming what differs */
+int ac_policy_pool_compatible(const ac_policy_config_t* pool_cfg, int32_t pool_form, const ac_policy_config_t* cfg, int32_t form);
+int ac_policy_pool_create(int32_t device_id, const ac_policy_config_t* cfg, int32_t form, int32_t capacity, ac_policy_pool_t** out);
+int ac_policy_pool_destroy(ac_policy_pool_t* p);
+/* member loads, refused as ac_policy_load / ac_policy_load_device refuse, keeping the member's previous weights. A member is loaded
+ * once a load of it has passed; an assignment reads that state when it is planned (assign after loading). */
+int ac_policy_pool_load(ac_policy_pool_t* p, int32_t member, const float* actor, int64_t n);
+int ac_policy_pool_load_device(ac_policy_pool_t* p, void* stream, int32_t member, const float* d_actor, int64_t n);
+int ac_policy_pool_load_refused(ac_policy_pool_t* p, void* stream, int32_t* refused);
+/* a policy's packed actor, device to device on `stream`; refused when the form, precision or configuration differ */
+int ac_policy_pool_copy_from(ac_policy_pool_t* p, void* stream, int32_t member, ac_policy_t* policy);
+int ac_policy_pool_packed(ac_policy_pool_t* p, int32_t member, void** d_ptr, int64_t* floats);
+/* the assignment: d_members [E] int32, member of each env (-1: its rows are not acted for), for calls of E * na rows (na rows per env).
+ * Copied and planned on `stream` (a stable sort of the rows by member, tiles of <= 32 rows of one member); the plan is kept for every
+ * later ac_policy_pool_act, and rebuilt by a call whose na differs. */
+int ac_policy_pool_assign(ac_policy_pool_t* p, void* stream, const int32_t* d_members, int64_t E, int32_t na);
+/* waits for `stream`: the first env whose member is out of range or not loaded (-1: none; such envs are not acted for) and the plan's
+ * tile count, which later act calls then use as their grid */
+int ac_policy_pool_check(ac_policy_pool_t* p, void* stream, int32_t* bad_env, int32_t* ntiles);
+/* the plan on the host (the device's code): order [E * na] call rows, tiles [3 * ac_policy_pool_max_tiles] {member, p0, p1} = rows
+ * order[p0 .. p1 - 1]; loaded [capacity] or NULL (all loaded) */
+int ac_policy_pool_plan_host(const int32_t* members, int64_t E, int32_t na, int32_t capacity, const int32_t* loaded, int32_t* order,
+                             int32_t* tiles, int32_t* ntiles, int32_t* bad_env);
+int ac_policy_pool_max_tiles(int64_t E, int32_t na, int32_t capacity, int64_t* out);
+/* 1 (the default): deal a member's tiles to workgroups that share blockIdx.x % 8 (one XCD's L2); 0: member-major order. Speed only. */
+int ac_policy_pool_set_tile_order(ac_policy_pool_t* p, int32_t xcd);
+/* one launch on `stream`: ac_policy_get_actions' actor part (rows, obs, masks, states, actions, log-probs as there; rows->n = E * na of
+ * the assignment) with each row's member; draws keyed by (seed, counter, call row, head) like ac_policy_get_actions. Unassigned rows'
+ * actions, states and log-probs are left untouched. */
+int ac_policy_pool_act(ac_policy_pool_t* p, void* stream, const ac_policy_rows_t* rows, const float* d_obs, const float* d_h_in,
+                       const float* d_masks, int32_t deterministic, uint64_t seed, uint64_t counter, float* d_actions, float* d_logp,
+                       float* d_h_out);
+
 const char* ac_last_error(void);
 const char* ac_version(void);
 
