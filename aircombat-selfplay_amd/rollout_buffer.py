@@ -162,24 +162,38 @@ class DeviceReplayBuffer:
     # names of the per-step arrays of a mini-batch, in the order the reference yields them
     _BATCH = ("obs", "actions", "masks", "action_log_probs", "advantages", "returns", "value_preds")
 
-    def minibatch(self, chunks, data_chunk_length):
-        """One mini-batch for the given chunk indices (host numpy arrays in the reference's order and shapes)."""
+    def minibatch(self, chunks, data_chunk_length, on_device=False):
+        """One mini-batch for the given chunk indices (host numpy arrays in the reference's order and shapes). With on_device=True
+        the same arrays, bit for bit, as float32 torch tensors on the buffer's GPU, gathered in HBM (no copy across PCIe).
+
+        The gather runs on the buffer's own stream. Torch's caching allocator may hand out memory that work queued on torch's
+        current stream still reads, so that stream is waited for first; the gather then ends with a wait for the buffer's stream,
+        and the tensors are complete, safe to read on any stream, when they are returned."""
         chunks = np.ascontiguousarray(chunks, dtype=np.int32)
         n, L = len(chunks), int(data_chunk_length)
         widths = {"obs": self.obs_shape, "share_obs": self.share_obs_shape, "actions": self.act_shape, "masks": (1,), "active_masks": (1,),
                   "action_log_probs": self._shapes["action_log_probs"][3:], "advantages": (1,), "returns": (1,), "value_preds": (1,)}
-        outs = {k: np.empty((L * n,) + tuple(widths[k]), dtype=np.float32) for k in self._BATCH}
+        shapes = {k: (L * n,) + tuple(widths[k]) for k in self._BATCH}
         hid = (self.recurrent_hidden_layers, self.recurrent_hidden_size)
-        outs["rnn_states_actor"], outs["rnn_states_critic"] = np.empty((n,) + hid, np.float32), np.empty((n,) + hid, np.float32)
-        batch = AcBufferBatch(**{k: v.ctypes.data for k, v in outs.items()})
-        self._ok(self.lib.ac_buffer_minibatch(self._h, chunks.ctypes.data, n, L, C.byref(batch), 0), "ac_buffer_minibatch")
+        shapes["rnn_states_actor"], shapes["rnn_states_critic"] = (n,) + hid, (n,) + hid
+        if on_device:
+            import torch
+            dev = torch.device("cuda", self.device_id)
+            outs = {k: torch.empty(s, dtype=torch.float32, device=dev) for k, s in shapes.items()}
+            torch.cuda.current_stream(dev).synchronize()
+            batch = AcBufferBatch(**{k: v.data_ptr() for k, v in outs.items()})
+        else:
+            outs = {k: np.empty(s, dtype=np.float32) for k, s in shapes.items()}
+            batch = AcBufferBatch(**{k: v.ctypes.data for k, v in outs.items()})
+        self._ok(self.lib.ac_buffer_minibatch(self._h, chunks.ctypes.data, n, L, C.byref(batch), int(bool(on_device))), "ac_buffer_minibatch")
         return tuple(outs[k] for k in self._BATCH) + (outs["rnn_states_actor"], outs["rnn_states_critic"])
 
     @staticmethod
-    def recurrent_generator(buffer, num_mini_batch, data_chunk_length, chunk_order=None):
+    def recurrent_generator(buffer, num_mini_batch, data_chunk_length, chunk_order=None, on_device=False):
         """ReplayBuffer.recurrent_generator(buffer, num_mini_batch, data_chunk_length) (buffer.py:169-268) for one buffer: the
         chunk permutation comes from torch.randperm like the reference's unless ``chunk_order`` is given (tests). The number of
-        chunks follows the reference: n_rollout_threads * buffer_size // data_chunk_length (the agent axis is not counted)."""
+        chunks follows the reference: n_rollout_threads * buffer_size // data_chunk_length (the agent axis is not counted).
+        on_device=True yields torch tensors on the buffer's GPU instead of numpy arrays (``minibatch``)."""
         self = buffer
         if isinstance(buffer, (list, tuple)):
             if len(buffer) != 1:
@@ -195,7 +209,7 @@ class DeviceReplayBuffer:
         chunk_order = np.asarray(chunk_order)
         self._ok(self.lib.ac_buffer_advantages(self._h), "ac_buffer_advantages")
         for i in range(int(num_mini_batch)):
-            yield self.minibatch(chunk_order[i * mb:(i + 1) * mb], L)
+            yield self.minibatch(chunk_order[i * mb:(i + 1) * mb], L, on_device=on_device)
 
 
 class DeviceSharedReplayBuffer(DeviceReplayBuffer):
@@ -212,7 +226,7 @@ class DeviceSharedReplayBuffer(DeviceReplayBuffer):
         return super().insert(obs, actions, rewards, masks, action_log_probs, value_preds, rnn_states_actor, rnn_states_critic,
                               bad_masks=bad_masks, share_obs=share_obs, active_masks=active_masks, on_device=on_device)
 
-    def recurrent_generator(self, advantages, num_mini_batch, data_chunk_length, chunk_order=None):   # noqa: signature of buffer.py:350
+    def recurrent_generator(self, advantages, num_mini_batch, data_chunk_length, chunk_order=None, on_device=False):   # noqa: buffer.py:350
         """buffer.recurrent_generator(buffer.advantages, num_mini_batch, data_chunk_length) (mappo/ppo_trainer.py:90). The
         advantages argument is the buffer's own normalised advantages in the reference's only call; the device copy is used."""
-        return DeviceReplayBuffer.recurrent_generator(self, num_mini_batch, data_chunk_length, chunk_order=chunk_order)
+        return DeviceReplayBuffer.recurrent_generator(self, num_mini_batch, data_chunk_length, chunk_order=chunk_order, on_device=on_device)

@@ -378,6 +378,21 @@ int ac_policy_pool_act(ac_policy_pool_t* p, void* stream, const ac_policy_rows_t
                        const float* d_masks, int32_t deterministic, uint64_t seed, uint64_t counter, float* d_actions, float* d_logp,
                        float* d_h_out);
 
+/* ---- the PPO update's GRU on the device ("The training GRU"): the recurrence of the reference's one-layer GRULayer,
+ * input and hidden 128, torch's gate order (r, z, n), over N chunks of T steps, rows T-major ([T * N, .], row t * N + j = step t of
+ * chunk j). One launch per call on `stream`, returning at once; every pointer is a device pointer of float32. Each step starts from
+ * h_in = h_{t-1} * masks[t * N + j]. Refused: a NULL required pointer, N or T < 1, N * T beyond the kernels' 32-bit row index. */
+/* forward: d_gi [T*N, 384] = x W_ihᵀ + b_ih, d_hxs [N, 128], d_masks [T*N], d_w_hh [384, 128], d_b_hh [384] -> d_y [T*N, 128] (the
+ * outputs before the LayerNorm), d_h_T [N, 128]; d_saved [T*N, 512] (r, z, n, W_hn h_in + b_hn) for a backward, or NULL */
+int ac_gru_seq_forward(int32_t device_id, void* stream, int32_t N, int32_t T, const float* d_gi, const float* d_hxs, const float* d_masks,
+                       const float* d_w_hh, const float* d_b_hh, float* d_y, float* d_h_T, float* d_saved);
+/* backward: upstream d_dy [T*N, 128] and d_dh_T [N, 128] (either NULL = zero), the forward's d_saved and d_y, its d_hxs, d_masks and
+ * d_w_hh -> d_dgi, d_dgh [T*N, 384] (gradients of the input-side and hidden-side gate pre-activations; they differ in the n block
+ * only) and d_dhxs [N, 128] (NULL: not computed) */
+int ac_gru_seq_backward(int32_t device_id, void* stream, int32_t N, int32_t T, const float* d_dy, const float* d_dh_T, const float* d_saved,
+                        const float* d_y, const float* d_hxs, const float* d_masks, const float* d_w_hh, float* d_dgi, float* d_dgh,
+                        float* d_dhxs);
+
 const char* ac_last_error(void);
 const char* ac_version(void);
 
