@@ -14,11 +14,12 @@ from .snapshot import EnvSnapshot, MultiSnapshot, SnapshotMismatch  # noqa: F401
 from .policy import DevicePolicy, DeviceMAPPOPolicy, DevicePolicyPool, UnsupportedPolicy  # noqa: F401
 from . import sharding  # noqa: F401
 
-_TORCH_EXPORTS = {"DeviceGRUFunction": "gru_train", "DeviceGRULayer": "gru_train", "use_device_gru": "gru_train"}
+_TORCH_EXPORTS = {"DeviceGRUFunction": "gru_train", "DeviceGRULayer": "gru_train", "use_device_gru": "gru_train",
+                  "DeviceMLPBlockFunction": "mlp_train", "DeviceMLPLayer": "mlp_train", "mlp_block": "mlp_train", "use_device_mlp": "mlp_train"}
 
 
 def __getattr__(name):
-    # the training GRU's classes derive from torch's: loaded on first use, so importing the package does not import torch
+    # the training layers' classes derive from torch's: loaded on first use, so importing the package does not import torch
     if name in _TORCH_EXPORTS:
         import importlib
         return getattr(importlib.import_module("." + _TORCH_EXPORTS[name], __name__), name)
@@ -27,4 +28,5 @@ def __getattr__(name):
 __all__ = ["AcConfig", "AcInitState", "Lib", "load_library", "library_path", "HipExtensionMissing",
            "config_from_yaml", "default_config", "default_nvn_config", "TASK_IDS", "HipVecEnv", "HipShareVecEnv", "MultiDeviceVecEnv", "make_env", "controller_forward",
            "DeviceReplayBuffer", "DeviceSharedReplayBuffer", "EnvSnapshot", "MultiSnapshot", "SnapshotMismatch",
-           "DevicePolicy", "DeviceMAPPOPolicy", "DevicePolicyPool", "UnsupportedPolicy", "DeviceGRUFunction", "DeviceGRULayer", "use_device_gru"]
+           "DevicePolicy", "DeviceMAPPOPolicy", "DevicePolicyPool", "UnsupportedPolicy", "DeviceGRUFunction", "DeviceGRULayer", "use_device_gru",
+           "DeviceMLPBlockFunction", "DeviceMLPLayer", "mlp_block", "use_device_mlp"]

@@ -162,6 +162,9 @@ SIGNATURES = {
     "ac_policy_pool_act": (C.c_int, [_p, _p, _p, _p, _p, _p, C.c_int32, C.c_uint64, C.c_uint64, _p, _p, _p]),
     "ac_gru_seq_forward": (C.c_int, [C.c_int32, _p, C.c_int32, C.c_int32, _p, _p, _p, _p, _p, _p, _p, _p]),
     "ac_gru_seq_backward": (C.c_int, [C.c_int32, _p, C.c_int32, C.c_int32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "ac_mlp_block_workspace_floats": (C.c_int64, [C.c_int32, C.c_int32]),
+    "ac_mlp_block_forward": (C.c_int, [C.c_int32, _p, C.c_int32, C.c_int32, C.c_float, _p, _p, _p, _p, _p, _p, _p]),
+    "ac_mlp_block_backward": (C.c_int, [C.c_int32, _p, C.c_int32, C.c_int32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     "ac_last_error": (C.c_char_p, []),
     "ac_version": (C.c_char_p, []),
     # include/aircombat_buffer.h

@@ -1,0 +1,195 @@
+"""The PPO / MAPPO update's MLP layers on the device ("The training MLP blocks").
+
+``DeviceMLPLayer`` is a drop-in for the reference's ``MLPLayer`` (algorithms/utils/mlp.py) with the same single child ``fc``
+(``nn.Sequential`` of ``Linear, ReLU, LayerNorm`` triples) and so the same state_dict keys. Each triple runs as one fused HIP kernel
+forward and one backward (csrc/mlp_train.hpp) on torch's current stream: ``y = LayerNorm(relu(x Wᵀ + b))`` without ``z`` or
+``relu(z)`` ever reaching memory, and a backward that recomputes ``z`` and sums the parameter gradients in a fixed order.
+
+``use_device_mlp(policy)`` swaps every MLPLayer-shaped module of a policy for a ``DeviceMLPLayer`` reusing the same ``fc``, so
+Parameter objects, optimiser state and checkpoints are unchanged. It composes with ``use_device_gru`` in either order. The optional
+``feature_norm``, the GRU layer's ``norm``, the heads, the loss and the optimiser stay torch.
+"""
+import torch
+import torch.nn as nn
+
+from . import capi
+from .policy import UnsupportedPolicy
+
+HID = 128      # out-features of every block, the LayerNorm's width
+K_MAX = 256    # in-features at most
+
+
+def _call(what, rc, lib):
+    if rc != 0:
+        raise RuntimeError(f"{what} failed: {lib.last_error()}")
+
+
+class DeviceMLPBlockFunction(torch.autograd.Function):
+    """(x [M, K], W [128, K], b, gamma, beta [128], eps, save) -> y [M, 128] = LayerNorm(relu(x Wᵀ + b)) * gamma + beta.
+
+    With ``save`` the forward also keeps the rows' mean and 1/std (8 bytes per row) and the backward recomputes ``z`` from ``x``.
+    ``dx`` is computed only when ``x`` requires grad. ``apply`` is called through ``mlp_block``, which decides ``save``: inside
+    ``forward`` grad mode is always off and ``needs_input_grad`` ignores it."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, gamma, beta, eps, save):
+        lib = capi.load_library()
+        x, w, b, gamma, beta = x.contiguous(), w.contiguous(), b.contiguous(), gamma.contiguous(), beta.contiguous()
+        M, K = x.shape
+        dev = x.device
+        y = torch.empty((M, HID), dtype=torch.float32, device=dev)
+        stats = torch.empty((M, 2), dtype=torch.float32, device=dev) if save else None
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _call("ac_mlp_block_forward", lib.ac_mlp_block_forward(dev.index, stream, M, K, eps, x.data_ptr(), w.data_ptr(), b.data_ptr(),
+                                                               gamma.data_ptr(), beta.data_ptr(), y.data_ptr(),
+                                                               None if stats is None else stats.data_ptr()), lib)
+        if save:
+            ctx.save_for_backward(x, w, b, gamma, stats)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        lib = capi.load_library()
+        x, w, b, gamma, stats = ctx.saved_tensors
+        M, K = x.shape
+        dev = x.device
+        dy = dy.contiguous()
+        new = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)
+        # the partial sums live in a torch tensor: torch's allocator orders its reuse on this stream
+        ws = new(lib.ac_mlp_block_workspace_floats(M, K))
+        dx = new(M, K) if ctx.needs_input_grad[0] else None
+        dw, db, dgamma, dbeta = new(HID, K), new(HID), new(HID), new(HID)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _call("ac_mlp_block_backward", lib.ac_mlp_block_backward(dev.index, stream, M, K, dy.data_ptr(), x.data_ptr(), w.data_ptr(),
+                                                                 b.data_ptr(), gamma.data_ptr(), stats.data_ptr(), ws.data_ptr(),
+                                                                 None if dx is None else dx.data_ptr(), dw.data_ptr(), db.data_ptr(),
+                                                                 dgamma.data_ptr(), dbeta.data_ptr()), lib)
+        return dx, dw, db, dgamma, dbeta, None, None
+
+
+def check_block(linear, act, norm, where="fc", device=True):
+    """UnsupportedPolicy unless (linear, act, norm) is a block the kernels run: nn.Linear K -> 128 with bias and K <= 256, nn.ReLU,
+    nn.LayerNorm(128) with affine parameters, float32; with ``device``, also on a CUDA device (checked at call time, so a policy can
+    be swapped before it is moved). ``act`` None: the caller applies the kernel's ReLU whatever the module list says (mlp_block)."""
+    bad = []
+    if not isinstance(linear, nn.Linear):
+        bad.append(f"not an nn.Linear ({type(linear).__name__})")
+    else:
+        if linear.out_features != HID:
+            bad.append(f"out-features {linear.out_features} (only {HID})")
+        if not 1 <= linear.in_features <= K_MAX:
+            bad.append(f"in-features {linear.in_features} (at most {K_MAX})")
+        if linear.bias is None:
+            bad.append("Linear without bias")
+        if linear.weight.dtype != torch.float32:
+            bad.append(f"dtype {linear.weight.dtype} (only float32)")
+        if device and linear.weight.device.type != "cuda":
+            bad.append(f"device {linear.weight.device} (only a CUDA device)")
+    if act is not None and not isinstance(act, nn.ReLU):
+        bad.append(f"activation {type(act).__name__} (only ReLU, activation_id 1)")
+    if not isinstance(norm, nn.LayerNorm):
+        bad.append(f"not an nn.LayerNorm ({type(norm).__name__})")
+    else:
+        if tuple(norm.normalized_shape) != (HID,):
+            bad.append(f"LayerNorm over {tuple(norm.normalized_shape)} (only ({HID},))")
+        if norm.weight is None or norm.bias is None:
+            bad.append("LayerNorm without affine parameters")
+        elif norm.weight.dtype != torch.float32:
+            bad.append(f"LayerNorm dtype {norm.weight.dtype} (only float32)")
+        elif device and norm.weight.device.type != "cuda":
+            bad.append(f"LayerNorm device {norm.weight.device} (only a CUDA device)")
+    if bad:
+        raise UnsupportedPolicy(f"{where}: " + ", ".join(bad))
+
+
+def mlp_block(x, linear, norm, where="mlp_block"):
+    """``norm(relu(linear(x)))`` as one fused kernel: x [..., K] float32 on the parameters' device -> [..., 128]. Something is saved
+    for a backward only when grad mode is on and x or a parameter requires grad."""
+    check_block(linear, None, norm, where)
+    if x.dtype != torch.float32 or x.device != linear.weight.device:
+        raise UnsupportedPolicy(f"{where}: input {x.dtype} on {x.device} (only float32 on {linear.weight.device})")
+    if x.shape[-1] != linear.in_features:
+        raise ValueError(f"{where}: input has {x.shape[-1]} features, the Linear takes {linear.in_features}")
+    lead = x.shape[:-1]
+    x2 = x.reshape(-1, linear.in_features)
+    if x2.shape[0] == 0:
+        return x.new_empty(lead + (HID,))
+    args = (x2, linear.weight, linear.bias, norm.weight, norm.bias)
+    save = torch.is_grad_enabled() and any(t.requires_grad for t in args)
+    return DeviceMLPBlockFunction.apply(*args, float(norm.eps), save).view(lead + (HID,))
+
+
+def _triples(fc):
+    return [(fc[j], fc[j + 1], fc[j + 2]) for j in range(0, len(fc), 3)]
+
+
+def _fc_shaped(fc):
+    return isinstance(fc, nn.Sequential) and len(fc) > 0 and len(fc) % 3 == 0 and \
+        all(isinstance(l, nn.Linear) and isinstance(n, nn.LayerNorm) for l, _, n in _triples(fc))
+
+
+def check_fc(fc, where="fc", device=True):
+    if not _fc_shaped(fc):
+        raise UnsupportedPolicy(f"{where}: not an nn.Sequential of (Linear, activation, LayerNorm) triples")
+    for j, (lin, act, norm) in enumerate(_triples(fc)):
+        check_block(lin, act, norm, f"{where}.{3 * j}", device)
+
+
+class DeviceMLPLayer(nn.Module):
+    """MLPLayer(input_dim, hidden_size, activation_id) of the reference with every block on the device: one child ``fc``
+    (nn.Sequential of Linear, ReLU, LayerNorm triples), forward(x [..., input_dim]) -> [..., 128]. ``hidden_size`` is the reference's
+    string of widths ("128 128"); only activation_id 1 (ReLU) is supported. Given ``fc``, that module is used as it is
+    (use_device_mlp)."""
+
+    def __init__(self, input_dim=HID, hidden_size="128 128", activation_id=1, fc=None):
+        super().__init__()
+        if fc is None:
+            if activation_id != 1:
+                raise UnsupportedPolicy(f"{type(self).__name__}: activation_id {activation_id} (only 1, ReLU)")
+            size = [input_dim] + list(map(int, str(hidden_size).split(" ")))
+            active = nn.ReLU()
+            mods = []
+            for j in range(len(size) - 1):
+                mods += [nn.Linear(size[j], size[j + 1]), active, nn.LayerNorm(size[j + 1])]
+            fc = nn.Sequential(*mods)
+        check_fc(fc, type(self).__name__ + ".fc", device=False)
+        self.fc = fc
+        self._size = [fc[0].in_features] + [lin.out_features for lin, _, _ in _triples(fc)]
+        self._hidden_layers = len(self._size) - 1
+
+    def forward(self, x):
+        for j, (lin, _, norm) in enumerate(_triples(self.fc)):
+            x = mlp_block(x, lin, norm, f"{type(self).__name__}.fc.{3 * j}")
+        return x
+
+    @property
+    def output_size(self):
+        return self._size[-1]
+
+
+def _mlp_layer_shaped(m):
+    return not isinstance(m, DeviceMLPLayer) and _fc_shaped(getattr(m, "fc", None))
+
+
+def use_device_mlp(module):
+    """Swap every MLPLayer-shaped module (one whose ``fc`` is an nn.Sequential of Linear, activation, LayerNorm triples) under
+    ``module`` for a DeviceMLPLayer holding the very same ``fc``. ``module`` is an nn.Module (``policy.actor``, ``policy.critic``) or
+    an object with ``actor`` / ``critic`` modules (the reference's PPO and MAPPO ``PPOPolicy``). Every layer is checked before any is
+    swapped; an unsupported one raises UnsupportedPolicy naming it. Returns the number of layers swapped."""
+    roots = [(module, "")] if isinstance(module, nn.Module) else \
+        [(getattr(module, k), k + ".") for k in ("actor", "critic") if isinstance(getattr(module, k, None), nn.Module)]
+    if not roots:
+        raise UnsupportedPolicy(f"{type(module).__name__}: neither an nn.Module nor an object with actor / critic modules")
+    found = []
+    for root, prefix in roots:
+        if _mlp_layer_shaped(root):
+            raise UnsupportedPolicy(f"{prefix or type(root).__name__}: an MLPLayer itself cannot be swapped in place; pass the module holding it")
+        for pname, parent in root.named_modules():
+            for cname, child in parent.named_children():
+                if _mlp_layer_shaped(child):
+                    found.append((parent, cname, child, prefix + (pname + "." if pname else "") + cname))
+    for _, _, child, where in found:
+        check_fc(child.fc, where + ".fc", device=False)
+    for parent, cname, child, _ in found:
+        setattr(parent, cname, DeviceMLPLayer(fc=child.fc))
+    return len(found)

@@ -393,6 +393,22 @@ int ac_gru_seq_backward(int32_t device_id, void* stream, int32_t N, int32_t T, c
                         const float* d_y, const float* d_hxs, const float* d_masks, const float* d_w_hh, float* d_dgi, float* d_dgh,
                         float* d_dhxs);
 
+/* ---- the PPO update's MLP layers on the device ("The training MLP blocks"): one block of the reference's MLPLayer,
+ * y = LayerNorm_128(relu(x Wᵀ + b)) * gamma + beta, x [M, K], W [128, K] (nn.Linear's layout), b, gamma, beta [128], biased variance.
+ * Every pointer is a device pointer of float32; the calls launch on `stream` and return at once. Refused: a NULL required pointer,
+ * M < 1, K outside 1 .. 256, M * 128 beyond the kernels' 32-bit index. */
+/* floats of ac_mlp_block_backward's d_workspace for this shape (one set of parameter-gradient partial sums per workgroup); -1: refused */
+int64_t ac_mlp_block_workspace_floats(int32_t M, int32_t K);
+/* forward, one launch: -> d_y [M, 128]; d_stats [M, 2] (mean and 1 / sqrt(var + eps) of relu(z) per row) for a backward, or NULL */
+int ac_mlp_block_forward(int32_t device_id, void* stream, int32_t M, int32_t K, float eps, const float* d_x, const float* d_w, const float* d_b,
+                         const float* d_gamma, const float* d_beta, float* d_y, float* d_stats);
+/* backward, two launches (the block's kernel, then the fixed-order sum of its partials): upstream d_dy [M, 128], the forward's d_x and
+ * d_stats -> d_dx [M, K] (NULL: not computed), d_dw [128, K], d_db, d_dgamma, d_dbeta [128]. z is recomputed from x, W, b; eps is
+ * already in d_stats. Results are bit-identical from run to run (no atomics). */
+int ac_mlp_block_backward(int32_t device_id, void* stream, int32_t M, int32_t K, const float* d_dy, const float* d_x, const float* d_w,
+                          const float* d_b, const float* d_gamma, const float* d_stats, float* d_workspace, float* d_dx, float* d_dw,
+                          float* d_db, float* d_dgamma, float* d_dbeta);
+
 const char* ac_last_error(void);
 const char* ac_version(void);
 
