@@ -43,6 +43,20 @@ class AcBufferBatch(C.Structure):
                                           "value_preds", "rnn_states_actor", "rnn_states_critic")]
 
 
+# ---- include/aircombat_rollout.h
+AC_ROLLOUT_NO_OPPONENT, AC_ROLLOUT_OPPONENT_POLICY, AC_ROLLOUT_OPPONENT_POOL = 0, 1, 2
+
+
+class AcRolloutConfig(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("na", "opponent_kind", "learner_deterministic", "opponent_deterministic")]
+
+
+class AcRolloutPostStep(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("E", "A", "na", "obs_dim", "env_act_dim", "act_dim", "hidden", "T", "s")] + \
+               [(n, C.c_void_p) for n in ("obs", "rewards", "actions", "dones", "OBS", "REWARDS", "ACTIONS", "MASKS", "RNN_ACTOR", "RNN_CRITIC",
+                                          "opp_h", "opp_masks")]
+
+
 class AcInitState(C.Structure):
     _fields_ = [(n, C.c_double) for n in
                 ("lon_deg", "lat_geod_deg", "h_sl_ft", "psi_deg", "u_fps", "v_fps", "w_fps",
@@ -181,6 +195,12 @@ SIGNATURES = {
     "ac_buffer_read": (C.c_int, [_p, C.c_int32, _p]),
     "ac_buffer_write_slot": (C.c_int, [_p, C.c_int32, C.c_int32, _p]),
     "ac_buffer_last_kernel_ms": (C.c_int, [_p, C.POINTER(C.c_float)]),
+    # include/aircombat_rollout.h
+    "ac_rollout_create": (C.c_int, [_p, _p, _p, _p, _p, C.POINTER(_p)]),
+    "ac_rollout_destroy": (C.c_int, [_p]),
+    "ac_rollout_opponent_state": (C.c_int, [_p, C.POINTER(_p), C.POINTER(_p)]),
+    "ac_rollout_collect": (C.c_int, [_p, _p, C.c_int32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64]),
+    "ac_rollout_post_step_host": (C.c_int, [_p]),
 }
 
 

@@ -65,6 +65,7 @@ struct Args {
   // row r of the call is env row (r / na) * A + a0 + r % na of the obs / action buffers (the agent range [a0, a0 + na) of an [E, A, .]
   // layout; a plain [n, .] layout is na = A = 1, a0 = 0)
   int na, A, a0;
+  int obs_compact;             // policy_kernel only: 1 = obs is a compact [n][obs_dim] array (a rollout buffer slot) while the actions keep the env rows
   int n_cat, n_shoot, use_fn, deterministic;
   int cat_off[MAXCAT], cat_cnt[MAXCAT];
   unsigned long long seed, counter;
@@ -604,7 +605,7 @@ __global__ __launch_bounds__(512) void policy_kernel(pol::Args a) {
     hv[4] = h1.x * mk; hv[5] = h1.y * mk; hv[6] = h1.z * mk; hv[7] = h1.w * mk;
   }
   if (spart == 0) {
-    const float* ob = a.obs + senv * a.obs_dim;
+    const float* ob = a.obs + (a.obs_compact ? (long long)sn : senv) * a.obs_dim;
     float x[MAXOBS];
 #pragma unroll
     for (int k = 0; k < MAXOBS; ++k) x[k] = k < a.obs_dim ? ob[k] : 0.0f;
