@@ -57,6 +57,13 @@ class AcRolloutPostStep(C.Structure):
                                           "opp_h", "opp_masks")]
 
 
+# ---- include/aircombat_rollout_share.h (its config is AcRolloutConfig)
+class AcShareRolloutPostStep(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("E", "A", "na", "obs_dim", "env_act_dim", "act_dim", "hidden", "T", "s")] + \
+               [(n, C.c_void_p) for n in ("obs", "rewards", "actions", "dones", "logp", "OBS", "SHARE_OBS", "REWARDS", "ACTIONS", "LOGP", "MASKS",
+                                          "ACTIVE_MASKS", "RNN_ACTOR", "RNN_CRITIC", "opp_h", "opp_masks")]
+
+
 class AcInitState(C.Structure):
     _fields_ = [(n, C.c_double) for n in
                 ("lon_deg", "lat_geod_deg", "h_sl_ft", "psi_deg", "u_fps", "v_fps", "w_fps",
@@ -201,6 +208,12 @@ SIGNATURES = {
     "ac_rollout_opponent_state": (C.c_int, [_p, C.POINTER(_p), C.POINTER(_p)]),
     "ac_rollout_collect": (C.c_int, [_p, _p, C.c_int32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64]),
     "ac_rollout_post_step_host": (C.c_int, [_p]),
+    # include/aircombat_rollout_share.h
+    "ac_share_rollout_create": (C.c_int, [_p, _p, _p, _p, _p, C.POINTER(_p)]),
+    "ac_share_rollout_destroy": (C.c_int, [_p]),
+    "ac_share_rollout_opponent_state": (C.c_int, [_p, C.POINTER(_p), C.POINTER(_p)]),
+    "ac_share_rollout_collect": (C.c_int, [_p, _p, C.c_int32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64]),
+    "ac_share_rollout_post_step_host": (C.c_int, [_p]),
 }
 
 

@@ -276,13 +276,13 @@ int ac_policy_packed(ac_policy_t* h, int32_t net, void** d_ptr, int64_t* floats)
 }  // extern "C"
 namespace {
 // checks and the launch of one policy call, either form. actor = false: a critic-only launch (get_values). obs_compact: d_obs is a
-// compact [n][obs_dim] array whatever the agent range says (the rollout collector's buffer slot). The critic reads the
+// compact [n][obs_dim] array whatever the agent range says (the rollout collectors' buffer slot, either form). The critic reads the
 // obs rows (the PPO form), or (the wide form) cent_mode's input: explicit rows d_cin + r * cent_dim, or each env's obs block.
 int policy_launch(ac_policy_t* h, void* stream, const ac_policy_rows_t* rows, const std::string& what, bool actor, bool critic,
                   const float* d_obs, const float* d_cin, int32_t cent_mode, const float* d_rnn_actor, const float* d_rnn_critic,
                   const float* d_masks, int32_t deterministic, uint64_t seed, uint64_t counter, float* d_values, float* d_actions,
                   float* d_logp, float* d_rnn_actor_out, float* d_rnn_critic_out, int obs_compact = 0) {
-  if (obs_compact && (h->wide || !actor)) return fail(what + ": compact obs rows are the PPO form's get_actions launch only");
+  if (obs_compact && !actor) return fail(what + ": compact obs rows are for get_actions launches only");
   if (critic && !h->cfg.has_critic) return fail(what + ": the policy was created without a critic");
   if ((actor && !h->loaded[0]) || (critic && !h->loaded[1])) return fail(what + ": weights not loaded");
   if (rows->n < 0 || rows->n > (1 << 24)) return fail(what + ": n must be in 0 .. 2^24");

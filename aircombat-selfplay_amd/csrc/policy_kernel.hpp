@@ -65,7 +65,7 @@ struct Args {
   // row r of the call is env row (r / na) * A + a0 + r % na of the obs / action buffers (the agent range [a0, a0 + na) of an [E, A, .]
   // layout; a plain [n, .] layout is na = A = 1, a0 = 0)
   int na, A, a0;
-  int obs_compact;             // policy_kernel only: 1 = obs is a compact [n][obs_dim] array (a rollout buffer slot) while the actions keep the env rows
+  int obs_compact;             // get_actions launches (not the pool's): 1 = obs is a compact [n][obs_dim] array (a rollout buffer slot) while the actions keep the env rows
   int n_cat, n_shoot, use_fn, deterministic;
   int cat_off[MAXCAT], cat_cnt[MAXCAT];
   unsigned long long seed, counter;
@@ -311,7 +311,7 @@ __device__ __forceinline__ void policy_body(const pol::Args& a, const pol::Wide&
   } else {
     // ---- the wide input: thread (row, part) stages columns 128 kb + 8 part .. + 7 of every 128-column K-block
     const int D = wx.dim[net], kp = wx.kpad[net], nst = kp / 32;
-    const float* __restrict__ xin = net == 0 ? a.obs + senv * D : wx.cin + (long long)(sn / wx.cna) * wx.cstride;
+    const float* __restrict__ xin = net == 0 ? a.obs + (a.obs_compact ? (long long)sn : senv) * D : wx.cin + (long long)(sn / wx.cna) * wx.cstride;
     if (net == 0 && a.n_shoot && spart == 0) {   // the prior reads the actor's raw obs (ppo_actor.py; thresholds as above)
       const float ang = xin[11] * 57.29577951308232f, dist = xin[13] * 10000.0f;
       ab0[srow][0] = dist <= 8000.0f ? 10.0f : (dist <= 12000.0f ? 6.0f : 3.0f);

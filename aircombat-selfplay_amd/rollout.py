@@ -1,4 +1,5 @@
-"""A whole rollout of the reference's PPO runners queued on the device in one call (include/aircombat_rollout.h).
+"""A whole rollout of the reference's runners queued on the device in one call (include/aircombat_rollout.h for the PPO runners,
+include/aircombat_rollout_share.h for the MAPPO share runner).
 
 ``DeviceRollout`` ties a ``HipVecEnv``, a ``DevicePolicy`` (with a critic), a ``DeviceReplayBuffer`` and, for self-play, an actor-only
 ``DevicePolicy`` or a ``DevicePolicyPool`` together. ``collect(n)`` then queues n steps of the runners' loop -- ``collect()``, the env
@@ -8,8 +9,15 @@ that does what ``insert`` and ``ReplayBuffer.insert`` do (csrc/rollout_collect.h
 loop of INTEGRATION.md §5d on the same handles.
 
 Everything runs on the env's stream, ordered on the device after the work already queued on the caller's stream and the buffer's, and
-before whatever is queued on either afterwards. Out of scope: the MAPPO form (``DeviceMAPPOPolicy`` / ``DeviceSharedReplayBuffer``),
-the per-step ``infos`` history, ``MultiDeviceVecEnv`` (one ``DeviceRollout`` per device) and graph capture.
+before whatever is queued on either afterwards.
+
+``DeviceMAPPORollout`` is the same for runner/share_jsbsim_runner.py: a ``HipShareVecEnv`` (or ``HipVecEnv``), a ``DeviceMAPPOPolicy``,
+a ``DeviceSharedReplayBuffer`` and, for self-play, an actor-only ``DeviceMAPPOPolicy`` or a ``DevicePolicyPool(form="mappo")``. Its
+post-step kernel (csrc/rollout_share_collect.hpp) also writes ``share_obs``, ``active_masks`` and the log-probs once per head column;
+the results are bit for bit those of the stepwise loop of INTEGRATION.md §5e.
+
+Out of scope for both: the per-step ``infos`` history, ``MultiDeviceVecEnv`` (one collector per device) and graph capture; for the
+MAPPO form also the mutual-support ``Discriminator``, whose intrinsic rewards change ``rewards`` before ``insert``.
 """
 import ctypes as C
 
@@ -27,6 +35,12 @@ class DeviceRollout:
     a reset; ``after_update`` carries them over). The handles must stay open while the collector is. A refusal (sizes, devices or forms
     that do not fit, a range past the buffer's end) raises ``ValueError`` and changes nothing."""
 
+    _abi = "ac_rollout"            # prefix of the C functions: create, destroy, opponent_state, collect
+    _opponent_doc = "a DevicePolicy(critic=False) or a DevicePolicyPool"
+
+    def _c(self, name):
+        return getattr(self.lib, f"{self._abi}_{name}")
+
     def __init__(self, envs, policy, buffer, opponent=None, num_learner_agents=None, deterministic=False, opponent_deterministic=False):
         self.lib = envs.lib
         self.envs, self.policy, self.buffer, self.opponent = envs, policy, buffer, opponent
@@ -37,21 +51,21 @@ class DeviceRollout:
         elif isinstance(opponent, DevicePolicy):
             kind = AC_ROLLOUT_OPPONENT_POLICY
         else:
-            raise TypeError("opponent is None, a DevicePolicy(critic=False) or a DevicePolicyPool")
+            raise TypeError(f"opponent is None, {self._opponent_doc}")
         A = envs.num_agents
         self.num_learner_agents = int(num_learner_agents) if num_learner_agents is not None else (A if opponent is None else A // 2)
         self.device_id = int(policy.device_id)
         cfg = AcRolloutConfig(self.num_learner_agents, kind, int(bool(deterministic)), int(bool(opponent_deterministic)))
         h = C.c_void_p()
         self._h = None
-        if self.lib.ac_rollout_create(envs._h, policy._h, buffer._h, None if opponent is None else opponent._h, C.byref(cfg), C.byref(h)) != 0:
+        if self._c("create")(envs._h, policy._h, buffer._h, None if opponent is None else opponent._h, C.byref(cfg), C.byref(h)) != 0:
             raise ValueError(self.lib.last_error())
         self._h = h
         self._opp_rows = envs.num_envs * (A - self.num_learner_agents)
 
     def close(self):
         if getattr(self, "_h", None):
-            self.lib.ac_rollout_destroy(self._h)
+            self._c("destroy")(self._h)
             self._h = None
 
     def __del__(self):
@@ -65,7 +79,7 @@ class DeviceRollout:
         if self.opponent is None:
             return None
         h, m = C.c_void_p(), C.c_void_p()
-        self.lib.check(self.lib.ac_rollout_opponent_state(self._h, C.byref(h), C.byref(m)), "ac_rollout_opponent_state")
+        self.lib.check(self._c("opponent_state")(self._h, C.byref(h), C.byref(m)), f"{self._abi}_opponent_state")
         n = self._opp_rows
         shape, ptr = ((n, 1, HID), h) if which == 0 else ((n, 1), m)
         holder = type("_View", (), {})()
@@ -108,9 +122,9 @@ class DeviceRollout:
         n_steps = int(n_steps)
         tstream, raw = self._stream(stream)
         opp = self.opponent
-        rc = self.lib.ac_rollout_collect(self._h, raw, n_steps, C.c_uint64(self.policy.seed & _U64), C.c_uint64(self.policy.counter & _U64),
-                                         C.c_uint64((opp.seed if opp is not None else 0) & _U64),
-                                         C.c_uint64((opp.counter if opp is not None else 0) & _U64))
+        rc = self._c("collect")(self._h, raw, n_steps, C.c_uint64(self.policy.seed & _U64), C.c_uint64(self.policy.counter & _U64),
+                                C.c_uint64((opp.seed if opp is not None else 0) & _U64),
+                                C.c_uint64((opp.counter if opp is not None else 0) & _U64))
         done = n_steps if rc == 0 else (self.buffer.step - before) % T
         self.policy.counter += done
         if opp is not None:
@@ -129,8 +143,27 @@ class DeviceRollout:
         b, T = self.buffer, self.buffer.buffer_size
         stream = getattr(self, "_last_stream", None) or torch.cuda.current_stream(torch.device("cuda", self.device_id))
         with torch.cuda.stream(stream):
-            next_values = self.policy.get_values(b.device_tensor("obs")[T].reshape(-1, self.policy.obs_dim),
-                                                 b.device_tensor("rnn_states_critic")[T], b.device_tensor("masks")[T])
+            next_values = self.policy.get_values(self._critic_input(T), b.device_tensor("rnn_states_critic")[T], b.device_tensor("masks")[T])
         stream.synchronize()   # the buffer copies next_values on its own stream
         b.compute_returns(next_values, on_device=True)
         return next_values
+
+    def _critic_input(self, t):
+        """the critic's input rows of buffer slot ``t``"""
+        return self.buffer.device_tensor("obs")[t].reshape(-1, self.policy.obs_dim)
+
+
+class DeviceMAPPORollout(DeviceRollout):
+    """``DeviceMAPPORollout(envs, policy, buffer, opponent=None, num_learner_agents=None)``: ``DeviceRollout`` for the share runner
+    (runner/share_jsbsim_runner.py). ``envs`` is a ``HipShareVecEnv`` or a ``HipVecEnv`` (only the handle is used), ``policy`` a
+    ``DeviceMAPPOPolicy`` whose critic is ``num_agents * obs_dim`` wide, ``buffer`` a ``DeviceSharedReplayBuffer`` and ``opponent`` None,
+    a ``DeviceMAPPOPolicy(critic=False)`` or a ``DevicePolicyPool(form="mappo")``. The buffer's slot at ``buffer.step`` must hold the
+    observations and the share observations the env is about to act on (``set_slot("obs", 0, obs[:, :na])`` and
+    ``set_slot("share_obs", 0, share_obs[:, :na])`` after a reset). ``collect``, ``compute_returns`` (``get_values`` on ``share_obs`` of the
+    last slot), ``opponent_states``, ``opponent_masks`` and ``close`` are ``DeviceRollout``'s."""
+
+    _abi = "ac_share_rollout"
+    _opponent_doc = "a DeviceMAPPOPolicy(critic=False) or a DevicePolicyPool(form=\"mappo\")"
+
+    def _critic_input(self, t):
+        return self.buffer.device_tensor("share_obs")[t].reshape(-1, self.policy.cent_obs_dim)
