@@ -64,6 +64,26 @@ class AcShareRolloutPostStep(C.Structure):
                                           "ACTIVE_MASKS", "RNN_ACTOR", "RNN_CRITIC", "opp_h", "opp_masks")]
 
 
+# ---- include/aircombat_eval.h
+AC_EVAL_NO_OPPONENT, AC_EVAL_OPPONENT_POLICY, AC_EVAL_OPPONENT_POOL, AC_EVAL_MAX_EPISODES = 0, 1, 2, 64
+
+
+class AcEvalConfig(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("na", "opponent_kind", "learner_deterministic", "opponent_deterministic", "episodes_per_env")]
+
+
+class AcEvalState(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("E", "A", "na", "K", "step", "pad_")] + \
+               [(n, C.c_void_p) for n in ("lrn_h", "lrn_masks", "opp_h", "opp_masks", "cum", "len", "count", "log_ret", "log_len", "log_end",
+                                          "remaining")]
+
+
+class AcEvalPostStep(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("E", "A", "na", "hidden", "K", "step")] + \
+               [(n, C.c_void_p) for n in ("rewards", "dones", "lrn_h", "lrn_masks", "opp_h", "opp_masks", "cum", "len", "count", "log_ret",
+                                          "log_len", "log_end", "remaining")]
+
+
 class AcInitState(C.Structure):
     _fields_ = [(n, C.c_double) for n in
                 ("lon_deg", "lat_geod_deg", "h_sl_ft", "psi_deg", "u_fps", "v_fps", "w_fps",
@@ -214,6 +234,13 @@ SIGNATURES = {
     "ac_share_rollout_opponent_state": (C.c_int, [_p, C.POINTER(_p), C.POINTER(_p)]),
     "ac_share_rollout_collect": (C.c_int, [_p, _p, C.c_int32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64]),
     "ac_share_rollout_post_step_host": (C.c_int, [_p]),
+    # include/aircombat_eval.h
+    "ac_eval_create": (C.c_int, [_p, _p, _p, _p, C.POINTER(_p)]),
+    "ac_eval_destroy": (C.c_int, [_p]),
+    "ac_eval_begin": (C.c_int, [_p, _p]),
+    "ac_eval_run": (C.c_int, [_p, _p, C.c_int32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64]),
+    "ac_eval_state": (C.c_int, [_p, _p]),
+    "ac_eval_post_step_host": (C.c_int, [_p]),
 }
 
 

@@ -2815,3 +2815,4 @@ int ac_get_missile(ac_env_t* h, int32_t env, int32_t agent, int32_t k, double ou
 #include "mlp_train.hpp"
 #include "rollout_collect.hpp"
 #include "rollout_share_collect.hpp"
+#include "eval_collect.hpp"

@@ -27,6 +27,25 @@ from .policy import DevicePolicy, DevicePolicyPool, HID
 _U64 = 2 ** 64 - 1
 
 
+def device_view(ptr, shape, device_id, typestr="<f4"):
+    """torch view of device memory a collector or evaluator owns: ``shape`` elements of ``typestr`` at ``ptr`` on ``cuda:device_id``."""
+    import torch
+    holder = type("_View", (), {})()
+    holder.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": typestr, "data": (int(ptr), False), "version": 2}
+    return torch.as_tensor(holder, device=f"cuda:{device_id}")
+
+
+def stream_of(device_id, stream):
+    """(torch stream object, raw handle) of ``stream``: a ``torch.cuda.Stream``, a raw ``hipStream_t`` value, or None = torch's current."""
+    import torch
+    dev = torch.device("cuda", device_id)
+    if stream is None:
+        stream = torch.cuda.current_stream(dev)
+    elif not hasattr(stream, "cuda_stream"):
+        stream = torch.cuda.default_stream(dev) if int(stream) == 0 else torch.cuda.ExternalStream(int(stream), device=dev)
+    return stream, stream.cuda_stream
+
+
 class DeviceRollout:
     """``DeviceRollout(envs, policy, buffer, opponent=None, num_learner_agents=None)``: the learner ``policy`` owns agents
     ``[0, num_learner_agents)`` of every env (default: all of them without an opponent, the first half with one) and ``buffer`` holds
@@ -75,16 +94,13 @@ class DeviceRollout:
             pass
 
     def _opponent_view(self, which):
-        import torch
         if self.opponent is None:
             return None
         h, m = C.c_void_p(), C.c_void_p()
         self.lib.check(self._c("opponent_state")(self._h, C.byref(h), C.byref(m)), f"{self._abi}_opponent_state")
         n = self._opp_rows
         shape, ptr = ((n, 1, HID), h) if which == 0 else ((n, 1), m)
-        holder = type("_View", (), {})()
-        holder.__cuda_array_interface__ = {"shape": shape, "typestr": "<f4", "data": (ptr.value, False), "version": 2}
-        return torch.as_tensor(holder, device=f"cuda:{self.device_id}")
+        return device_view(ptr.value, shape, self.device_id)
 
     @property
     def opponent_states(self):
@@ -97,14 +113,7 @@ class DeviceRollout:
         return self._opponent_view(1)
 
     def _stream(self, stream):
-        """(torch stream object, raw handle) of ``stream``: a ``torch.cuda.Stream``, a raw ``hipStream_t`` value, or None = torch's current."""
-        import torch
-        dev = torch.device("cuda", self.device_id)
-        if stream is None:
-            stream = torch.cuda.current_stream(dev)
-        elif not hasattr(stream, "cuda_stream"):
-            stream = torch.cuda.default_stream(dev) if int(stream) == 0 else torch.cuda.ExternalStream(int(stream), device=dev)
-        return stream, stream.cuda_stream
+        return stream_of(self.device_id, stream)
 
     def collect(self, n_steps=None, stream=None):
         """Queue ``n_steps`` steps (default: the rest of the buffer) starting at ``buffer.step`` and return without waiting. ``stream``
