@@ -17,7 +17,8 @@ from .evaluate import DeviceEvaluator, EvalResult, elo_update  # noqa: F401
 from . import sharding  # noqa: F401
 
 _TORCH_EXPORTS = {"DeviceGRUFunction": "gru_train", "DeviceGRULayer": "gru_train", "use_device_gru": "gru_train",
-                  "DeviceMLPBlockFunction": "mlp_train", "DeviceMLPLayer": "mlp_train", "mlp_block": "mlp_train", "use_device_mlp": "mlp_train"}
+                  "DeviceMLPBlockFunction": "mlp_train", "DeviceMLPLayer": "mlp_train", "mlp_block": "mlp_train", "use_device_mlp": "mlp_train",
+                  "DeviceActEvalFunction": "act_train", "act_evaluate": "act_train", "use_device_act": "act_train"}
 
 
 def __getattr__(name):
@@ -31,4 +32,5 @@ __all__ = ["AcConfig", "AcInitState", "Lib", "load_library", "library_path", "Hi
            "config_from_yaml", "default_config", "default_nvn_config", "TASK_IDS", "HipVecEnv", "HipShareVecEnv", "MultiDeviceVecEnv", "make_env", "controller_forward",
            "DeviceReplayBuffer", "DeviceSharedReplayBuffer", "EnvSnapshot", "MultiSnapshot", "SnapshotMismatch",
            "DevicePolicy", "DeviceMAPPOPolicy", "DevicePolicyPool", "UnsupportedPolicy", "DeviceRollout", "DeviceMAPPORollout", "DeviceEvaluator", "EvalResult", "elo_update", "DeviceGRUFunction", "DeviceGRULayer", "use_device_gru",
-           "DeviceMLPBlockFunction", "DeviceMLPLayer", "mlp_block", "use_device_mlp"]
+           "DeviceMLPBlockFunction", "DeviceMLPLayer", "mlp_block", "use_device_mlp",
+           "DeviceActEvalFunction", "act_evaluate", "use_device_act"]

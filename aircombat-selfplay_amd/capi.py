@@ -116,6 +116,11 @@ class AcConfig(C.Structure):
     ]
 
 
+class AcActHeads(C.Structure):
+    """ac_act_heads_t: the training action heads' configuration (ac_act_eval_*)."""
+    _fields_ = [("n_cat", C.c_int32), ("nvec", C.c_int32 * 8), ("n_shoot_cols", C.c_int32)]
+
+
 # every symbol include/aircombat.h declares: (restype, argtypes)
 _p = C.c_void_p
 SIGNATURES = {
@@ -206,6 +211,9 @@ SIGNATURES = {
     "ac_mlp_block_workspace_floats": (C.c_int64, [C.c_int32, C.c_int32]),
     "ac_mlp_block_forward": (C.c_int, [C.c_int32, _p, C.c_int32, C.c_int32, C.c_float, _p, _p, _p, _p, _p, _p, _p]),
     "ac_mlp_block_backward": (C.c_int, [C.c_int32, _p, C.c_int32, C.c_int32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "ac_act_eval_workspace_floats": (C.c_int64, [C.POINTER(AcActHeads), C.c_int32]),
+    "ac_act_eval_forward": (C.c_int, [C.c_int32, _p, C.POINTER(AcActHeads), C.c_int32, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "ac_act_eval_backward": (C.c_int, [C.c_int32, _p, C.POINTER(AcActHeads), C.c_int32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     "ac_last_error": (C.c_char_p, []),
     "ac_version": (C.c_char_p, []),
     # include/aircombat_buffer.h

@@ -409,6 +409,35 @@ int ac_mlp_block_backward(int32_t device_id, void* stream, int32_t M, int32_t K,
                           const float* d_b, const float* d_gamma, const float* d_stats, float* d_workspace, float* d_dx, float* d_dw,
                           float* d_db, float* d_dgamma, float* d_dbeta);
 
+/* ---- the PPO update's action heads on the device ("The training action heads"): ACTLayer.evaluate_actions of the reference
+ * for n_cat Categorical heads (logits_net: W_h [nvec[h], 128], b_h [nvec[h]]) and, with n_shoot_cols 1 or 4, ONE BetaShootBernoulli head
+ * (net: W [2, 128], b [2]; the last module of action_outs) whose probability is applied to all the shoot columns. d_w / d_b (and d_dw /
+ * d_db) are HOST arrays of n_cat (+ 1 with shoot columns) device pointers, the shoot head last. x [M, 128]; actions [M, n_cat +
+ * n_shoot_cols] float32 as the buffer stores them; alpha0, beta0 [M] with shoot columns only. Every device pointer is float32; the calls
+ * launch on `stream` and return at once. Refused, each with its own message: a NULL required pointer, M < 1, n_cat outside 1 .. 8, a
+ * head size below 2, more than 160 categorical logits, n_shoot_cols not 0, 1 or 4, shoot columns without alpha0 / beta0, M * 128 beyond
+ * the kernels' 32-bit index. An action that is not an integer in 0 .. nvec[h] - 1 makes that row's logp NaN and touches nothing else: the
+ * taken logit is picked by compare-and-select, never by indexing; in the backward such an action matches no logit. */
+typedef struct {
+  int32_t n_cat;                        /* Categorical heads, 1 .. 8 */
+  int32_t nvec[8];                      /* their sizes, each >= 2, at most 160 in all */
+  int32_t n_shoot_cols;                 /* 0, 1 (MultiDiscrete + Discrete(2)) or 4 (MultiDiscrete + MultiDiscrete([2, 2, 2, 2])) */
+} ac_act_heads_t;
+/* floats of ac_act_eval_backward's d_workspace: one set of 129 * (sum nvec + 2 [shoot]) partial sums per workgroup, one workgroup per
+ * 32-row tile up to 256; -1: refused */
+int64_t ac_act_eval_workspace_floats(const ac_act_heads_t* heads, int32_t M);
+/* forward, one launch: -> d_logp [M] (sum over heads of the taken action's log-probability; the shoot head's summed over its columns)
+ * and d_ent [M] (sum over heads of the entropy, unscaled; the shoot head's counted once) */
+int ac_act_eval_forward(int32_t device_id, void* stream, const ac_act_heads_t* heads, int32_t M, const float* d_x, const float* const* d_w,
+                        const float* const* d_b, const float* d_actions, const float* d_alpha0, const float* d_beta0, float* d_logp,
+                        float* d_ent);
+/* backward, two launches (the heads' kernel, then the fixed-order sum of its partials): upstream d_dlogp, d_dent [M] (NULL: zero) ->
+ * d_dx [M, 128] (NULL: not computed), d_dw[h] [nvec[h], 128] and d_db[h] [nvec[h]] per head. The logits are recomputed from x. Results
+ * are bit-identical from run to run (no atomics). */
+int ac_act_eval_backward(int32_t device_id, void* stream, const ac_act_heads_t* heads, int32_t M, const float* d_dlogp, const float* d_dent,
+                         const float* d_x, const float* const* d_w, const float* const* d_b, const float* d_actions, const float* d_alpha0,
+                         const float* d_beta0, float* d_workspace, float* d_dx, float* const* d_dw, float* const* d_db);
+
 const char* ac_last_error(void);
 const char* ac_version(void);
 
