@@ -18,7 +18,8 @@ from . import sharding  # noqa: F401
 
 _TORCH_EXPORTS = {"DeviceGRUFunction": "gru_train", "DeviceGRULayer": "gru_train", "use_device_gru": "gru_train",
                   "DeviceMLPBlockFunction": "mlp_train", "DeviceMLPLayer": "mlp_train", "mlp_block": "mlp_train", "use_device_mlp": "mlp_train",
-                  "DeviceActEvalFunction": "act_train", "act_evaluate": "act_train", "use_device_act": "act_train"}
+                  "DeviceActEvalFunction": "act_train", "act_evaluate": "act_train", "use_device_act": "act_train",
+                  "DevicePPOLossFunction": "ppo_update", "ppo_loss": "ppo_update", "device_clip_adam_step": "ppo_update", "DevicePPOTrainer": "ppo_update"}
 
 
 def __getattr__(name):
@@ -33,4 +34,5 @@ __all__ = ["AcConfig", "AcInitState", "Lib", "load_library", "library_path", "Hi
            "DeviceReplayBuffer", "DeviceSharedReplayBuffer", "EnvSnapshot", "MultiSnapshot", "SnapshotMismatch",
            "DevicePolicy", "DeviceMAPPOPolicy", "DevicePolicyPool", "UnsupportedPolicy", "DeviceRollout", "DeviceMAPPORollout", "DeviceEvaluator", "EvalResult", "elo_update", "DeviceGRUFunction", "DeviceGRULayer", "use_device_gru",
            "DeviceMLPBlockFunction", "DeviceMLPLayer", "mlp_block", "use_device_mlp",
-           "DeviceActEvalFunction", "act_evaluate", "use_device_act"]
+           "DeviceActEvalFunction", "act_evaluate", "use_device_act",
+           "DevicePPOLossFunction", "ppo_loss", "device_clip_adam_step", "DevicePPOTrainer"]

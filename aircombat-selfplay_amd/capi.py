@@ -121,6 +121,15 @@ class AcActHeads(C.Structure):
     _fields_ = [("n_cat", C.c_int32), ("nvec", C.c_int32 * 8), ("n_shoot_cols", C.c_int32)]
 
 
+class AcOptimEntry(C.Structure):
+    """ac_optim_entry_t: one tensor of the optimiser's table (ac_optim_*)."""
+    _fields_ = [(n, C.c_void_p) for n in ("p", "g", "m", "v")] + [("numel", C.c_int64), ("group", C.c_int32), ("first_chunk", C.c_int32)] + \
+               [(n, C.c_double) for n in ("lr", "eps", "beta1", "beta2", "bias_correction1", "bias_correction2")]
+
+
+AC_PPO_STAT_LOSS, AC_PPO_STAT_POLICY_LOSS, AC_PPO_STAT_VALUE_LOSS, AC_PPO_STAT_ENTROPY_LOSS, AC_PPO_STAT_RATIO_MEAN, AC_PPO_STAT_DENOMINATOR = range(6)
+AC_PPO_NSTAT = 8
+
 # every symbol include/aircombat.h declares: (restype, argtypes)
 _p = C.c_void_p
 SIGNATURES = {
@@ -214,6 +223,14 @@ SIGNATURES = {
     "ac_act_eval_workspace_floats": (C.c_int64, [C.POINTER(AcActHeads), C.c_int32]),
     "ac_act_eval_forward": (C.c_int, [C.c_int32, _p, C.POINTER(AcActHeads), C.c_int32, _p, _p, _p, _p, _p, _p, _p, _p]),
     "ac_act_eval_backward": (C.c_int, [C.c_int32, _p, C.POINTER(AcActHeads), C.c_int32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "ac_ppo_loss_workspace_floats": (C.c_int64, [C.c_int32, C.c_int32]),
+    "ac_ppo_loss_forward": (C.c_int, [C.c_int32, _p, C.c_int32, C.c_int32, C.c_int32, _p, _p, _p, _p, _p, _p, _p, _p, C.c_double, C.c_double, C.c_double, C.c_int32,
+                                      _p, _p, _p, _p, _p]),
+    "ac_ppo_loss_backward": (C.c_int, [C.c_int32, _p, C.c_int32, C.c_int32, _p, _p, _p, C.c_double, _p, _p, _p]),
+    "ac_optim_workspace_floats": (C.c_int64, [_p, C.c_int32, C.c_int32]),
+    "ac_optim_grad_norms": (C.c_int, [C.c_int32, _p, _p, _p, C.c_int32, C.c_int32, _p, _p]),
+    "ac_optim_clip_adam_step": (C.c_int, [C.c_int32, _p, _p, _p, C.c_int32, C.c_int32, _p, C.c_double, C.c_int32]),
+    "ac_ppo_update_constant": (C.c_int32, [C.c_int32]),
     "ac_last_error": (C.c_char_p, []),
     "ac_version": (C.c_char_p, []),
     # include/aircombat_buffer.h

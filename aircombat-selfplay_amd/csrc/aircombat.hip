@@ -2814,6 +2814,7 @@ int ac_get_missile(ac_env_t* h, int32_t env, int32_t agent, int32_t k, double ou
 #include "gru_train.hpp"
 #include "mlp_train.hpp"
 #include "act_train.hpp"
+#include "ppo_update.hpp"
 #include "rollout_collect.hpp"
 #include "rollout_share_collect.hpp"
 #include "eval_collect.hpp"

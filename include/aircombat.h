@@ -438,6 +438,71 @@ int ac_act_eval_backward(int32_t device_id, void* stream, const ac_act_heads_t* 
                          const float* d_x, const float* const* d_w, const float* const* d_b, const float* d_actions, const float* d_alpha0,
                          const float* d_beta0, float* d_workspace, float* d_dx, float* const* d_dw, float* const* d_db);
 
+/* ---- the rest of the PPO update on the device ("The loss, the clip and Adam"): the reference's loss
+ * (algorithms/ppo/ppo_trainer.py:44-61), torch's clip_grad_norm_ per optimiser param group and torch's single-tensor Adam. Every device
+ * pointer is float32; the calls launch on `stream` and return at once. No floating-point atomics: results are bit-identical from run to
+ * run. Refused, each with its own message and before any launch: a NULL required pointer, M or n_ent < 1 or beyond the kernels' 32-bit
+ * index; for the optimiser, no entries or more than 512, n_groups outside 1 .. 8, an entry with a NULL or misaligned pointer, numel < 1,
+ * a group outside 0 .. n_groups - 1, or a first_chunk that ac_optim_workspace_floats did not lay out. */
+/* d_stats [AC_PPO_NSTAT]: */
+#define AC_PPO_STAT_LOSS 0
+#define AC_PPO_STAT_POLICY_LOSS 1
+#define AC_PPO_STAT_VALUE_LOSS 2
+#define AC_PPO_STAT_ENTROPY_LOSS 3   /* -mean(ent) */
+#define AC_PPO_STAT_RATIO_MEAN 4
+#define AC_PPO_STAT_DENOMINATOR 5    /* M, or the sum of d_active */
+#define AC_PPO_NSTAT 8
+/* floats of ac_ppo_loss_forward's d_workspace (five sums per workgroup); -1: refused */
+int64_t ac_ppo_loss_workspace_floats(int32_t M, int32_t n_ent);
+/* forward, two launches. Per row (each array [M]; d_old_logp [M, old_cols], 1 .. 64 columns against which logp broadcasts as in the
+ * reference, whose MAPPO buffer keeps one old log-probability per action column: the row's term is the sum over the columns and
+ * ratio.mean() runs over all M old_cols ratios): ratio = exp(logp - old_logp); min(ratio adv, clamp(ratio, 1 - c, 1 + c) adv);
+ * 0.5 max((v - R)^2, (vp + clamp(v - vp, -c, c) - R)^2), or 0.5 (R - v)^2 with use_clipped_value_loss 0. Both means are plain means, or
+ * with d_active [M] (NULL: none) sum(. active) / sum(active); the entropy term is -mean(d_ent [n_ent]) always. loss = policy +
+ * value_loss_coef value + entropy_coef entropy_loss. -> d_stats, d_loss [1] (NULL: not written; the loss again, for a caller that
+ * keeps it in a tensor of its own), and d_dlogp, d_dvalues [M]: dloss/dlogp and dloss/dvalues for a unit
+ * upstream gradient (torch's conventions: clamp passes the gradient on its closed interval, min / max split a tie evenly);
+ * dloss/dent is the constant -entropy_coef / n_ent. */
+int ac_ppo_loss_forward(int32_t device_id, void* stream, int32_t M, int32_t n_ent, int32_t old_cols, const float* d_logp,
+                        const float* d_old_logp, const float* d_adv, const float* d_values, const float* d_value_preds, const float* d_returns, const float* d_active,
+                        const float* d_ent, double clip_param, double value_loss_coef, double entropy_coef, int32_t use_clipped_value_loss,
+                        float* d_workspace, float* d_stats, float* d_loss, float* d_dlogp, float* d_dvalues);
+/* backward, one launch: d_upstream [1] (a device scalar) times the forward's d_dlogp, d_dvalues and the entropy's constant ->
+ * d_g_logp, d_g_values [M], d_g_ent [n_ent] (each may be NULL: not computed) */
+int ac_ppo_loss_backward(int32_t device_id, void* stream, int32_t M, int32_t n_ent, const float* d_upstream, const float* d_dlogp,
+                         const float* d_dvalues, double entropy_coef, float* d_g_logp, float* d_g_values, float* d_g_ent);
+
+/* One entry of the optimiser's tensor table per parameter that has a gradient: any 4-byte-aligned device pointers (vector loads are
+ * used where all four are 16-byte aligned), numel >= 1. The work is cut into chunks of 2048 elements of one tensor, one workgroup each,
+ * so the launch count does not depend on the number of tensors. The same bytes serve as the host table (checked, laid out) and as its
+ * device copy (read by the kernels): fill it in pinned memory, call ac_optim_workspace_floats, then copy it to the device on `stream`. */
+typedef struct {
+  float* p;                  /* the parameter, */
+  float* g;                  /* its gradient (rewritten with the clipped gradient), */
+  float* m;                  /* exp_avg and */
+  float* v;                  /* exp_avg_sq */
+  int64_t numel;
+  int32_t group;             /* the optimiser's param group, 0 .. n_groups - 1: one norm and one clip coefficient per group */
+  int32_t first_chunk;       /* written by ac_optim_workspace_floats */
+  double lr, eps, beta1, beta2;
+  double bias_correction1;   /* 1 - beta1^step and */
+  double bias_correction2;   /* 1 - beta2^step of THIS tensor after its step count was incremented, computed by the host in double */
+} ac_optim_entry_t;
+/* checks the table, writes every first_chunk and returns the floats of d_workspace (two per chunk); -1: refused */
+int64_t ac_optim_workspace_floats(ac_optim_entry_t* entries, int32_t n_entries, int32_t n_groups);
+/* two launches (the chunks' sums of squares, then their fixed-order sum): d_norms [n_groups] = the L2 norm of each group's gradients
+ * (0 for a group without entries), left in device memory. `entries` is the host table, `d_entries` its device copy. */
+int ac_optim_grad_norms(int32_t device_id, void* stream, const ac_optim_entry_t* entries, const ac_optim_entry_t* d_entries, int32_t n_entries,
+                        int32_t n_groups, float* d_workspace, float* d_norms);
+/* one launch: per group coef = min(1, max_grad_norm / (norm + 1e-6)) as torch's clip_grad_norm_ (a NaN norm gives a NaN coefficient;
+ * with use_max_grad_norm 0 the coefficient is 1), g <- g coef, then torch's single-tensor Adam: m <- m + (1 - beta1)(g - m),
+ * v <- beta2 v + (1 - beta2) g^2, p <- p - (lr / bias_correction1) m / (sqrt(v) / sqrt(bias_correction2) + eps). */
+int ac_optim_clip_adam_step(int32_t device_id, void* stream, const ac_optim_entry_t* entries, const ac_optim_entry_t* d_entries,
+                            int32_t n_entries, int32_t n_groups, const float* d_norms, double max_grad_norm, int32_t use_max_grad_norm);
+/* the kernels' constants, for callers that size tests and tables by them: 0 rows of the loss per workgroup pass, 1 its workgroups at
+ * most, 2 elements per optimiser chunk, 3 entries at most, 4 groups at most; -1 otherwise */
+int32_t ac_ppo_update_constant(int32_t which);
+
 const char* ac_last_error(void);
 const char* ac_version(void);
 
