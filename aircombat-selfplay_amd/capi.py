@@ -160,6 +160,7 @@ SIGNATURES = {
     "ac_set_status": (C.c_int, [_p, C.c_int32, C.c_int32, C.c_int32]),
     "ac_get_entity": (C.c_int, [_p, C.c_int32, C.c_int32, C.POINTER(C.c_double)]),
     "ac_get_missile": (C.c_int, [_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_double)]),
+    "ac_get_missile_target": (C.c_int, [_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
     "ac_timing_begin": (C.c_int, [_p]),
     "ac_timing_end": (C.c_int, [_p, C.POINTER(C.c_float)]),
     "ac_step_timed_device": (C.c_int, [_p, _p, C.POINTER(C.c_float), C.POINTER(C.c_float)]),

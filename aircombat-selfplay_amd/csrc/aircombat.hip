@@ -2803,6 +2803,19 @@ int ac_get_missile(ac_env_t* h, int32_t env, int32_t agent, int32_t k, double ou
   }
   return 0;
 }
+int ac_get_missile_target(ac_env_t* h, int32_t env, int32_t agent, int32_t k, int32_t* target) {
+  if (check_idx(h, env, agent) || !target) return fail("ac_get_missile_target: bad argument");
+  if (host_entry(h)) return -1;
+  if (k < 0 || k >= h->dc.msl_slots) return fail("ac_get_missile_target: no such missile slot");
+  HIP_OK(hipSetDevice(h->device));
+  HIP_OK(hipStreamSynchronize(h->stream));
+  const size_t N = h->N, n = (size_t)env * h->A + agent;
+  if (h->A == 2) { *target = 1 - agent; return 0; }   // 1v1: agent.enemies[0]
+  int order;
+  HIP_OK(hipMemcpy(&order, h->dp.MI + ((size_t)k * NMI + MI_order) * N + n, sizeof order, hipMemcpyDeviceToHost));
+  *target = order & 15;   // the launch wrote its target's index within the env into the low bits of `order`
+  return 0;
+}
 
 }  // extern "C"
 

@@ -719,6 +719,12 @@ class HipVecEnv:
         self.lib.check(self.lib.ac_get_missile(self._h, env, agent, k, out), "ac_get_missile")
         return np.array(out[:], dtype=np.float64)
 
+    def get_missile_target(self, env, agent, k):
+        """Index within the env of the aircraft that munition slot k of an agent was launched at (ac_get_missile_target)."""
+        out = C.c_int32()
+        self.lib.check(self.lib.ac_get_missile_target(self._h, env, agent, k, C.byref(out)), "ac_get_missile_target")
+        return int(out.value)
+
 
 class HipShareVecEnv(HipVecEnv):
     """The Share* VecEnv family (envs/env_wrappers.py:323-462) for MultipleCombat: ``reset()`` -> ``(obs, share_obs)``,

@@ -172,6 +172,8 @@ int ac_set_status(ac_env_t* h, int32_t env, int32_t agent, int32_t status);
 int ac_get_entity(ac_env_t* h, int32_t env, int32_t agent, double out[12]);
 /* missile k of an agent: status, N,E,U, vN,vE,vU, theta, psi, t, mass, model (0 AIM-9L, 1 AIM-120B, 2 AIM-9M) (MissileSimulator, simulatior.py:393-608) */
 int ac_get_missile(ac_env_t* h, int32_t env, int32_t agent, int32_t k, double out[12]);
+/* the aircraft (index within the env) that missile k of an agent was launched at (MissileSimulator.target_aircraft); meaningless for a slot never launched */
+int ac_get_missile_target(ac_env_t* h, int32_t env, int32_t agent, int32_t k, int32_t* target);
 
 /* Order-independent 64-bit digest of all aircraft states on the device (sum over aircraft of a per-field hash): E envs in the
  * same state give E times the digest of one env (mod 2^64). Test / profiling aid: one read-only pass over the state arrays with

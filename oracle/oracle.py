@@ -83,6 +83,12 @@ def lib():
         L.or_env_get_pose.argtypes = [C.c_void_p, C.c_int, dp]
         L.or_env_num_missiles.argtypes = [C.c_void_p]
         L.or_env_get_missile.argtypes = [C.c_void_p, C.c_int, dp]
+        L.or_env_get_missile_ext.argtypes = [C.c_void_p, C.c_int, dp]
+        L.or_env_set_missile_target.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        L.or_env_set_missile_status.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        L.or_env_round_missile_f32.argtypes = [C.c_void_p, C.c_int]
+        L.or_env_num_chaff.argtypes = [C.c_void_p]
+        L.or_env_get_chaff.argtypes = [C.c_void_p, C.c_int, dp]
         L.or_env_status.argtypes = [C.c_void_p, C.c_int]
         L.or_env_set_status.argtypes = [C.c_void_p, C.c_int, C.c_int]
         L.or_env_bloods.argtypes = [C.c_void_p, C.c_int]
@@ -279,6 +285,40 @@ class OracleEnv:
             self.L.or_env_get_missile(self.p, k, out)
             res.append(np.array(out[:]))
         return res
+
+    def missiles_ext(self):
+        """Per munition: model (parameter set), dict key, still in the dict, recede count, last range to target, fuse radius."""
+        res = []
+        for k in range(self.L.or_env_num_missiles(self.p)):
+            out = (C.c_double * 6)()
+            self.L.or_env_get_missile_ext(self.p, k, out)
+            res.append(np.array(out[:]))
+        return res
+
+    def set_missile_target(self, k, target):
+        self.L.or_env_set_missile_target(self.p, k, target)
+
+    def set_missile_status(self, k, status):
+        self.L.or_env_set_missile_status(self.p, k, status)
+
+    def round_missiles_f32(self):
+        for k in range(self.L.or_env_num_missiles(self.p)):
+            self.L.or_env_round_missile_f32(self.p, k)
+
+    def chaff(self):
+        """Decoy clouds: N, E, U, age, status (1 = burnt out), releasing aircraft."""
+        res = []
+        for q in range(self.L.or_env_num_chaff(self.p)):
+            out = (C.c_double * 6)()
+            self.L.or_env_get_chaff(self.p, q, out)
+            res.append(np.array(out[:]))
+        return res
+
+    def counters(self, i):
+        """rem_gun, rem_9m, rem_120b, rem_chaff, bloods, status of aircraft i (the scenario tasks' weapon rules)."""
+        out = (C.c_double * 6)()
+        self.L.or_env_get_counters(self.p, i, out)
+        return np.array(out[:])
 
     def get_rnn(self, i):
         """(hidden[128], low_action[4]) of the low-level controller for aircraft i (hierarchical tasks)."""

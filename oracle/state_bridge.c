@@ -100,6 +100,23 @@ void or_env_get_missile(const OrEnv* e, int k, double out[14]) {
   out[4] = m->velocity[0]; out[5] = m->velocity[1]; out[6] = m->velocity[2];
   out[7] = m->posture[1]; out[8] = m->posture[2]; out[9] = m->t; out[10] = m->m; out[11] = m->parent; out[12] = m->target; out[13] = m->geodetic[2];
 }
+/* free-flight harness hooks (tests/open_loop_util.py): the rest of a munition's record; planted faults (retarget, forced status); a munition
+ * whose state is stored in float32 (the twin of a device whose munition slots are fp32); the decoy clouds */
+void or_env_get_missile_ext(const OrEnv* e, int k, double out[6]) {
+  const OrMissile* m = &e->msl[k];
+  out[0] = m->model; out[1] = m->key; out[2] = m->in_sims; out[3] = m->recede_count; out[4] = m->dist_prev; out[5] = m->Rc;
+}
+void or_env_set_missile_target(OrEnv* e, int k, int target) { e->msl[k].target = target; }
+void or_env_set_missile_status(OrEnv* e, int k, int status) { e->msl[k].status = status; }
+void or_env_round_missile_f32(OrEnv* e, int k) {
+  OrMissile* m = &e->msl[k];
+  for (int j = 0; j < 3; j++) { m->position[j] = (float)m->position[j]; m->velocity[j] = (float)m->velocity[j]; m->posture[j] = (float)m->posture[j]; }
+  m->t = (float)m->t; m->m = (float)m->m; m->dtheta = (float)m->dtheta; m->dphi = (float)m->dphi; m->dist_prev = (float)m->dist_prev;
+}
+int or_env_num_chaff(const OrEnv* e) { return e->n_chaff; }
+void or_env_get_chaff(const OrEnv* e, int q, double out[6]) {
+  out[0] = e->chaff[q].pos[0]; out[1] = e->chaff[q].pos[1]; out[2] = e->chaff[q].pos[2]; out[3] = e->chaff[q].t; out[4] = e->chaff[q].status; out[5] = e->chaff[q].parent;
+}
 int or_env_status(const OrEnv* e, int i) { return e->ac[i].status; }
 void or_env_set_status(OrEnv* e, int i, int status) { e->ac[i].status = status; }
 double or_env_bloods(const OrEnv* e, int i) { return e->ac[i].bloods; }

@@ -16,15 +16,9 @@ regime in which a tolerance can be stated, and is dropped from the comparison fr
 import numpy as np
 import pytest
 
-from open_loop_util import OpenLoopPair
+from open_loop_util import RANDOM_FORM_IDS, RANDOM_FORMS, RANDOM_STEPS, OpenLoopPair, assert_random_flight_conditions, envelope, fly, random_actions
 
 pytestmark = pytest.mark.gpu
-
-
-def envelope(k):
-    x = np.asarray(k, dtype=np.float64) / 600.0
-    return {"pos_m": 0.02 + 15.0 * x ** 3, "att_rad": 2e-4 + 0.015 * x ** 2, "vel_ms": 0.01 + 0.8 * x ** 2, "obs": 2e-4 + 0.015 * x ** 2,
-            "rew": 5e-3 + 0.02 * x ** 2}
 
 
 # every kernel form a BASELINE config launches: (id, task, aircraft per side, environment that pins the form)
@@ -41,6 +35,7 @@ FORMS = [
 
 
 FORM_IDS = [f[0].split(":")[0].split(" (")[0].replace(" ", "_").replace(",", "") for f in FORMS]
+assert [f[:4] for f in RANDOM_FORMS[:len(FORMS)]] == [tuple(f) for f in FORMS]     # the random-action cases fly these forms, and scenario1's two
 
 
 @pytest.mark.parametrize("form", FORMS + [("hierarchical C2: commands from the controller kernel", "hierarchical_singlecombat", 1, {})], ids=FORM_IDS + ["C2_hierarchical"])
@@ -154,4 +149,29 @@ def test_random_actions_open_loop_until_a_switch_differs(pkg, oracle):
     # factor 10): anything else is a termination bug, reported with the env, the step and both done rows
     assert not pair.unexplained, pair.unexplained
     assert (pair.horizon > 100).mean() >= 0.9          # the regime with a stated tolerance is the common case, not the exception
+    pair.close()
+
+
+@pytest.mark.parametrize("form", RANDOM_FORMS, ids=RANDOM_FORM_IDS)
+def test_random_actions_open_loop_every_form(pkg, oracle, monkeypatch, form):
+    """Random actions, free flight, munitions live, in EVERY kernel form (FORMS, and scenario1 in its quad and pair form): control indices
+    uniform and redrawn every 5 steps, every weapon / shoot column Bernoulli(0.05) redrawn every step, one fixed seed per form
+    (open_loop_util.RANDOM_FORMS: 32 envs of 1v1, 16 of 2v2, 8 of 4v4, 300 steps = 30 s each). After every step, for the envs inside their
+    horizon: the aircraft inside the 8x envelope in episode age, every munition still closing on its target inside the same envelope in
+    position and velocity against its twin (matched by parent and flight time; from its first receding step on only its discrete facts
+    are compared: at a near miss the pass turns a millimetre of target difference into decimetres), and no done flag and no weapon decision
+    (remaining rounds, shoot bookkeeping, scenario counters, a munition's status, target and model, the number in flight) that differs
+    without a threshold to explain it (OpenLoopPair.near_a_threshold). At the end, conditions: nine envs in ten comparable past step 100; in
+    the forms with weapon columns a munition flew in at least half of the envs and at least one ended inside an env's horizon. The fp32
+    twin meets all of them with these inputs (tests/test_open_loop_twin.py), and the seeds were chosen there.
+
+    Left out: the *_dodge_missile tasks (their rule-based launch never fires from STARTS under random actions, 0/32 in the twin: they stay
+    with the teacher-forced tests) and the hierarchical forms (a controller argmax flip is a decision of its own kind and wants a test of
+    its own)."""
+    name, task, per_side, pins, E, seed = form
+    for k, v in pins.items():
+        monkeypatch.setenv(k, v)
+    pair = OpenLoopPair(pkg, oracle, E, spread=True, task=task, per_side=per_side)
+    fly(pair, random_actions(task, pair.E, pair.A, RANDOM_STEPS, seed), name)
+    assert_random_flight_conditions(pair, task, RANDOM_STEPS)
     pair.close()
