@@ -60,3 +60,89 @@ def chaff_record(uid, color, alive, pose, model="CHF"):
     if alive:
         return aircraft_record(uid, color, pose, model)
     return f"-{uid}\n"
+
+
+def chaff_from_words(w0, w1):
+    """The chaff bookkeeping inside the scenario tasks' two packed extension words (csrc/scenario_kernel.hpp: n_ch in bits 2-3 of the
+    second word, the clouds' status bits 4 and 5, their multiplicities bits 6-10 and 11-15): (n_ch, ((status0, mult0), (status1, mult1)))."""
+    w1 = int(w1)
+    return (w1 >> 2) & 3, (((w1 >> 4) & 1, (w1 >> 6) & 31), ((w1 >> 5) & 1, (w1 >> 11) & 31))
+
+
+class FrameWriter:
+    """BaseEnv.render's bookkeeping for one env (env_base.py:207-250), one frame at a time: which munitions have shown their explosion
+    record (MissileSimulator.log writes it once), the order of env._tempsims (a uid keeps the dict position of its first launch), the
+    chaff clouds of env._chaffsims with the pose their parent had at the release, and env.reset() clearing all of it, seen as a
+    `cur_step` that does not increase. ``HipVecEnv.render`` feeds it from the host getters and ``FlightRecorder.write_acmi`` from
+    recorded frames; the text is the same because this is the only place that writes it.
+
+    ``frame(cur_step, entities, slots, chaff)`` returns the frame's text ('#time' line and one record per line):
+      entities[a]   ac_get_entity's values of aircraft a (at least the first six)
+      slots[a][k]   (status, model, px, py, pz, theta, psi) of munition slot k, model = ac_get_missile's out[11]; read for the slots
+                    the task's uids cover (the 1v1 missile tasks: min(num_missiles, 4); the scenario family: 2)
+      chaff[a]      (n_ch, ((status0, mult0), (status1, mult1))), see chaff_from_words; read for the scenario tasks only"""
+
+    def __init__(self, cfg, num_agents=None):
+        self.cfg = cfg
+        self.num_agents = int(num_agents if num_agents is not None else cfg.n_agents)
+        A, ne = self.num_agents, int(cfg.n_ego)
+        self.center = (cfg.center_lon, cfg.center_lat, cfg.center_alt)
+        self.uids = getattr(cfg, "uids", None) or [f"{'A' if a < ne else 'B'}0{(a if a < ne else a - ne) + 1}00" for a in range(A)]
+        self.colors = ["Blue" if a < ne else "Red" for a in range(A)]
+        task = int(cfg.task)
+        slots = {3: 4, 2: 4, 5: 2, 6: 2}.get(task, 0)          # AC_TASK_SHOOT_MISSILE, _DODGE_MISSILE, _SCENARIO1, _SCENARIO_NVN
+        self.radius = 300 if task in (3, 2) else 5             # MissileSimulator itself (300 m fuse) against the scenario munitions' 5 m
+        if task == 2 and int(cfg.n_agents) > 2:                # multiplecombat_dodge_missile: two uids per aircraft, like the scenario tasks
+            slots = 2
+        # a slot's uid is "agent + remaining count at the launch" (scenario1_task.py:83,92; singlecombat_with_missile_task.py:199): slots
+        # are consumed from the highest count down
+        self.n_slots = [min(int(cfg.num_missiles[a]), slots) if slots == 4 else slots for a in range(A)]
+        self.has_chaff = task in (5, 6)
+        self.last_step = -1
+        self.clear()
+
+    def clear(self):
+        self.exploded, self.first, self.chaff = set(), {}, {}
+
+    def frame(self, cur_step, entities, slots=None, chaff=None):
+        step = int(cur_step)
+        if step <= self.last_step:      # the episode was reset: env.reset() clears _tempsims / _chaffsims (env_base.py:98-113)
+            self.clear()
+        self.last_step = step
+        A, uids, colors = self.num_agents, self.uids, self.colors
+        msgs = [aircraft_record(uids[a], colors[a], entities[a]) for a in range(A)]
+        # env._tempsims in dict order = first-launch order of the uids
+        flying = []
+        for a in range(A):
+            for k in range(self.n_slots[a]):
+                m = slots[a][k]
+                if m[0] < 0:
+                    self.exploded.discard((a, k))
+                    continue
+                flying.append((a, k, m))
+        for a, k, _m in flying:
+            self.first.setdefault((a, k), (step, a))      # dict position of the uid: its first launch (step, agent order)
+        flying.sort(key=lambda r: self.first[(r[0], r[1])])
+        for a, k, m in flying:
+            uid = f"{uids[a]}{self.n_slots[a] - k}"
+            rec, boom = missile_records(uid, colors[a], int(m[0]), m[2:5], m[5], m[6], self.center, (a, k) in self.exploded,
+                                        self.radius, MISSILE_MODELS[int(m[1])])
+            if boom:
+                self.exploded.add((a, k))
+            msgs.append(rec)
+        # env._chaffsims: one ChaffSimulator per qualifying incoming missile of a release event, uid "agent + (remaining + 10)"
+        if self.has_chaff:
+            for a in range(A):
+                n_ch, clouds = chaff[a]
+                rem = int(self.cfg.num_missiles[a])
+                for q in range(min(int(n_ch), 2)):
+                    status, mult = clouds[q]
+                    for _ in range(int(mult)):
+                        uid = f"{uids[a]}{rem + 10}"
+                        rem -= 1
+                        if uid not in self.chaff:
+                            self.chaff[uid] = {"color": colors[a], "pose": tuple(entities[a][:6])}
+                        self.chaff[uid]["alive"] = int(status) == 0
+            for uid, ch in self.chaff.items():
+                msgs.append(chaff_record(uid, ch["color"], ch["alive"], ch["pose"]))
+        return f"#{step * self.cfg.agent_interaction_steps / self.cfg.sim_freq:.2f}\n" + "".join(msg + "\n" for msg in msgs)

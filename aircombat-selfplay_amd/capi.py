@@ -127,6 +127,23 @@ class AcOptimEntry(C.Structure):
                [(n, C.c_double) for n in ("lr", "eps", "beta1", "beta2", "bias_correction1", "bias_correction2")]
 
 
+class AcRecorderColumn(C.Structure):
+    """ac_recorder_column_t (include/aircombat_record.h)."""
+    _fields_ = [("name", C.c_char * 16), ("elem_size", C.c_int32), ("count", C.c_int32)]
+
+
+class AcRecorderLayout(C.Structure):
+    """ac_recorder_layout_t: the flight recorder's column table for one handle shape."""
+    _fields_ = [("n_columns", C.c_int32), ("bytes_per_aircraft_frame", C.c_int32), ("columns", AcRecorderColumn * 8)]
+
+
+class AcRecorderInfo(C.Structure):
+    """ac_recorder_info_t."""
+    _fields_ = [(n, C.c_int32) for n in ("task", "A", "msl_slots", "has_ext", "E", "S", "F", "attached")] + [("count", C.c_int64), ("bytes", C.c_int64)]
+
+
+AC_REC_DONE, AC_REC_AFTER_RESET = 1, 2
+
 AC_PPO_STAT_LOSS, AC_PPO_STAT_POLICY_LOSS, AC_PPO_STAT_VALUE_LOSS, AC_PPO_STAT_ENTROPY_LOSS, AC_PPO_STAT_RATIO_MEAN, AC_PPO_STAT_DENOMINATOR = range(6)
 AC_PPO_NSTAT = 8
 
@@ -267,6 +284,18 @@ SIGNATURES = {
     "ac_eval_run": (C.c_int, [_p, _p, C.c_int32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64]),
     "ac_eval_state": (C.c_int, [_p, _p]),
     "ac_eval_post_step_host": (C.c_int, [_p]),
+    # include/aircombat_record.h
+    "ac_recorder_layout": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(AcRecorderLayout)]),
+    "ac_recorder_create": (C.c_int, [_p, _p, C.c_int32, C.c_int32, C.POINTER(_p)]),
+    "ac_recorder_destroy": (C.c_int, [_p]),
+    "ac_recorder_bytes": (C.c_int, [_p, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
+    "ac_recorder_attach": (C.c_int, [_p, _p]),
+    "ac_recorder_detach": (C.c_int, [_p]),
+    "ac_recorder_capture": (C.c_int, [_p, C.c_int32]),
+    "ac_recorder_count": (C.c_int64, [_p]),
+    "ac_recorder_info": (C.c_int, [_p, C.POINTER(AcRecorderInfo)]),
+    "ac_recorder_read": (C.c_int, [_p, C.c_int32, C.c_int64, C.c_int32, _p]),
+    "ac_recorder_device_ptr": (C.c_int, [_p, C.c_int32, C.POINTER(_p), C.POINTER(C.c_int64)]),
 }
 
 

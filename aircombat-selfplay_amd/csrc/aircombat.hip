@@ -1700,6 +1700,7 @@ static uint64_t fnv1a(uint64_t hsh, const void* p, size_t n) {
 
 #include "aql_dispatch.hpp"
 
+struct ac_recorder;
 struct ac_env {
   ac_config_t cfg;
   DevCfg dc;
@@ -1741,6 +1742,7 @@ struct ac_env {
   // host steps as AQL packets on a queue of the handle's own (aql_dispatch.hpp)
   AqlState aql;
   bool stream_dirty;                     // work enqueued on `stream` since it was last synchronised: the next AQL dispatch synchronises it
+  ac_recorder* rec;                      // the attached flight recorder (flight_recorder.hpp), captured behind every step and reset; null: none
 };
 
 static void geodetic2ecef_m(double lat_deg, double lon_deg, double alt, double* x, double* y, double* z) {
@@ -1866,10 +1868,12 @@ static int launch_plan(ac_env* h, const StepPlan& sp) {   // through HIP, on the
   }
   return 0;
 }
+static int recorder_hook(ac_env* h, int after_reset);   // flight_recorder.hpp: one frame of the attached recorder, if there is one
 static int launch_step(ac_env* h, const float* d_actions, int host_set = -1) {
   StepPlan sp;
   if (step_plan(h, d_actions, host_set, &sp)) return -1;
-  return launch_plan(h, sp);
+  if (launch_plan(h, sp)) return -1;
+  return h->rec ? recorder_hook(h, 0) : 0;
 }
 // ---- the two directions of ordering between the handle's HIP stream and its AQL queue (aql_dispatch.hpp)
 static int aql_fault(ac_env* h, const std::string& e) {   // a queue that has faulted or timed out is not used again
@@ -1896,13 +1900,14 @@ static int host_entry(ac_env* h) {
   return 0;
 }
 // A host step: through the AQL queue once it is set up (and no timing bracket is open: bench.py times host steps with HIP events on the
-// stream), else through HIP; the first host step of a handle goes through HIP and sets the queue up after it.
+// stream), else through HIP; the first host step of a handle goes through HIP and sets the queue up after it. A handle with a flight
+// recorder attached takes its host steps through HIP launches: the capture is a launch on the stream, behind the step's.
 static int host_step(ac_env* h, int set) {
   if (aql_settle(h)) return -1;
   StepPlan sp;
   if (step_plan(h, nullptr, set, &sp)) return -1;
   AqlState& a = h->aql;
-  bool aql = a.mode == AqlState::READY && !h->timing && sp.n == a.nkern;
+  bool aql = a.mode == AqlState::READY && !h->timing && !h->rec && sp.n == a.nkern;
   for (int i = 0; aql && i < sp.n; ++i) aql = sp.k[i].fn == a.kern[i].fn;
   if (aql) {
     if (stream_settle(h)) return -1;
@@ -1910,6 +1915,7 @@ static int host_step(ac_env* h, int set) {
     return e.empty() ? 0 : aql_fault(h, e);
   }
   if (launch_plan(h, sp)) return -1;
+  if (h->rec && recorder_hook(h, 0)) return -1;
   if (a.mode == AqlState::PENDING && !h->timing) {   // the launch above has loaded HIP's code object: its kernel symbols can be resolved
     const std::string e = aql_setup(&a, h->device, sp);
     if (e.empty()) a.mode = AqlState::READY;
@@ -1932,6 +1938,8 @@ static int launch_reset(ac_env* h) {
   }
   return 0;
 }
+
+#include "flight_recorder.hpp"
 
 extern "C" {
 
@@ -2180,6 +2188,7 @@ int ac_destroy(ac_env_t* h) {
   (void)aql_settle(h);
   aql_release(&h->aql);          // the AQL queue, its signal and the kernarg blocks
   (void)hipStreamSynchronize(h->stream);
+  recorder_env_gone(h);
   void* bufs[] = {h->dp.F, h->dp.D, h->dp.MF, h->dp.MD, h->dp.MI, h->dp.obs, h->dp.rew, h->dp.done, h->dp.info,
                   h->d_actions, h->d_tab, h->d_tF, h->d_tD, h->d_state_io, h->d_XF, h->d_XI, h->dp.H, h->dp.man_step, h->dp.man_h0, h->d_ctlWs8, h->d_low, h->hp.HD, h->hp.HF, h->hp.HI, h->hp.HR,
                   h->d_idx, h->d_clone_tab, h->d_snap_hdr};
@@ -2207,6 +2216,7 @@ int ac_reset(ac_env_t* h, float* obs) {
   HIP_OK(hipStreamSynchronize(h->stream));    // (a step still in flight may yet write the error word)
   *h->err_host = 0; h->err_sticky = 0;
   if (launch_reset(h)) return -1;
+  if (h->rec && recorder_hook(h, 1)) return -1;
   if (obs) HIP_OK(hipMemcpyAsync(obs, h->dp.obs, sizeof(float) * (size_t)h->N * h->obs_dim, hipMemcpyDeviceToHost, h->stream));
   HIP_OK(hipStreamSynchronize(h->stream));
   return 0;
@@ -2472,15 +2482,10 @@ int ac_set_status(ac_env_t* h, int32_t env, int32_t agent, int32_t status) {
 
 __global__ void entity_kernel(DevPtrs P, DevCfg c, int n, double* out) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  State s; Task t; Derived d; Props pr;
-  load_state(P.F, P.I, P.D, c.N, n, s, t);
-  f16::locate(s, d); f16::body_frame(s, d);
-  make_props(s, d, c, pr);
-  const double R2D = 180.0 / 3.14159265358979323846;
-  out[0] = atan2(d.sLon64, d.cLon64) * R2D; out[1] = atan2(d.sLat64, d.cLat64) * R2D; out[2] = pr.alt_m;
-  out[3] = atan2f(pr.sphi, pr.cphi); out[4] = asinf(pr.stht);
-  float psi = atan2f(pr.m12, pr.m11); if (psi < 0.0f) psi += 2.0f * f16::kPi;
-  out[5] = psi; out[6] = pr.vn; out[7] = pr.ve; out[8] = pr.vd; out[9] = pr.n; out[10] = pr.e; out[11] = pr.u;
+  Task t;
+  double v[12];
+  entity_values(P, c, n, v, t);   // (flight_recorder.hpp: the body the capture kernel shares)
+  for (int i = 0; i < 12; ++i) out[i] = v[i];
 }
 int ac_get_entity(ac_env_t* h, int32_t env, int32_t agent, double out[12]) {
   if (check_idx(h, env, agent) || !out) return fail("ac_get_entity: bad argument");

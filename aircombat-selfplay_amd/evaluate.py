@@ -11,7 +11,10 @@ those of the stepwise loop of INTEGRATION.md §5d / §5e on the same handles.
 Every env logs its first ``episodes_per_env`` episodes. With a pool as the opponent, one pass evaluates against every assigned member
 at once (``pool.assign_split``), and ``EvalResult.per_opponent`` with ``elo_update`` restate selfplay_jsbsim_runner.py:203-227.
 
-Out of scope: ``render()`` / ACMI, ``MultiDeviceVecEnv`` (one evaluator per device), graph capture and the per-step ``infos`` history.
+ACMI recordings of evaluation episodes: attach a flight recorder to the env (``envs.record``, recorder.py) before the reset, and
+``episode_frames`` / ``write_episode_acmi`` turn a logged episode into its frames or its Tacview file once the evaluation has ended.
+
+Out of scope: ``MultiDeviceVecEnv`` (one evaluator per device), graph capture and the per-step ``infos`` history.
 """
 import collections
 import ctypes as C
@@ -197,6 +200,8 @@ class DeviceEvaluator:
         if self.lib.ac_eval_begin(self._h, raw) != 0:
             raise ValueError(self.lib.last_error())
         self._last_stream = tstream
+        rec = getattr(self.envs, "recorder", None)
+        self._rec, self._rec_c0 = rec, (rec.count if rec is not None else None)   # step t of this evaluation is recorder frame c0 + t
 
     def run(self, n_steps, stream=None):
         """Queue ``n_steps`` evaluation steps and return without waiting. ``stream`` (a ``torch.cuda.Stream``, a raw ``hipStream_t``
@@ -245,6 +250,37 @@ class DeviceEvaluator:
             if self.remaining() == 0:
                 break
         return self.result()
+
+    def episode_frames(self, env, k):
+        """(first, last): the recorder frames of the k-th logged episode of env ``env``, for ``FlightRecorder.frames`` / ``write_acmi``.
+        Step t of the evaluation (counted from ``begin()``) is frame ``c0 + t`` of the recorder that was attached to the env at
+        ``begin()``, ``c0`` its count then. An episode of length L whose last step was ``t_end`` is frames ``c0 + t_end - L`` ..
+        ``c0 + t_end - 1``: the first of them shows the reset state (the captured ``reset()``, or the step that ended the previous
+        episode and auto-reset the env), the last the state before the step that ended it; the frame of step ``t_end`` itself already
+        shows the next episode, as ``render()`` does after an auto-reset. Raises ``ValueError`` where no recorder was attached at
+        ``begin()``, the slot holds no episode, the episode started before recording did, or its frames have left the ring."""
+        from .recorder import check_span
+        rec, c0 = getattr(self, "_rec", None), getattr(self, "_rec_c0", None)
+        if rec is None or rec._h is None:
+            raise ValueError("episode_frames: no flight recorder was attached to the env at begin() (envs.record)")
+        res = self.result()
+        env, k = int(env), int(k)
+        if not (0 <= env < res.lengths.shape[0] and 0 <= k < res.lengths.shape[1] and res.logged[env, k]):
+            raise ValueError(f"episode_frames: env {env} has no logged episode {k}")
+        if env not in rec.envs:
+            raise ValueError(f"episode_frames: env {env} is not among the recorded envs")
+        L, t_end = int(res.lengths[env, k]), int(res.end_steps[env, k])
+        first, last = c0 + t_end - L, c0 + t_end - 1
+        if first < 0:
+            raise ValueError(f"episode_frames: episode {k} of env {env} started before recording did (record before the reset)")
+        check_span(rec.count, rec.capacity, first, last)
+        return first, last
+
+    def write_episode_acmi(self, path, env, k):
+        """Write the k-th logged episode of env ``env`` as a Tacview ACMI file (``FlightRecorder.write_acmi`` over ``episode_frames``).
+        Returns the number of frames written, the episode's length."""
+        first, last = self.episode_frames(env, k)
+        return self._rec.write_acmi(path, env, first, last)
 
     def result(self):
         """The log so far as an ``EvalResult`` (waits for the stream of the last ``begin`` / ``run``)."""

@@ -405,63 +405,49 @@ class HipVecEnv:
         if not getattr(self, "_acmi_started", False):
             with open(filepath, mode="w", encoding="utf-8-sig") as f:
                 f.write(acmi.HEADER)
-            self._acmi_started, self._acmi_exploded, self._acmi_chaff, self._acmi_first, self._acmi_step = True, set(), {}, {}, -1
-        if step <= self._acmi_step:      # the episode was reset: env.reset() clears _tempsims / _chaffsims (env_base.py:98-113)
-            self._acmi_exploded, self._acmi_chaff, self._acmi_first = set(), {}, {}
-        self._acmi_step = step
-        center = (cfg.center_lon, cfg.center_lat, cfg.center_alt)
-        uids = getattr(cfg, "uids", None) or [f"{'A' if a < cfg.n_ego else 'B'}0{(a if a < cfg.n_ego else a - cfg.n_ego) + 1}00" for a in range(self.num_agents)]
-        color = lambda a: "Blue" if a < cfg.n_ego else "Red"
-        msgs = []
+            self._acmi_started, self._acmi = True, acmi.FrameWriter(cfg, self.num_agents)   # (the bookkeeping write_acmi shares)
+        w = self._acmi
         entities = [self.get_entity(env, a) for a in range(self.num_agents)]
+        slots = []
         for a in range(self.num_agents):
-            msgs.append(acmi.aircraft_record(uids[a], color(a), entities[a]))
-        slots = {AC_TASK_SHOOT_MISSILE: 4, 2: 4, AC_TASK_SCENARIO1: 2, AC_TASK_SCENARIO_NVN: 2}.get(cfg.task, 0)
-        base_missile = cfg.task in (AC_TASK_SHOOT_MISSILE, 2)       # MissileSimulator itself (300 m fuse); 2 = AC_TASK_DODGE_MISSILE
-        if cfg.task == 2 and cfg.n_agents > 2:                      # multiplecombat_dodge_missile: two uids per aircraft, like the scenario tasks
-            slots = 2
-        # env._tempsims in dict order = first-launch order of the uids; a slot's uid is "agent + remaining count at the launch"
-        # (scenario1_task.py:83,92; singlecombat_with_missile_task.py:199): slots are consumed from the highest count down
-        flying = []
-        for a in range(self.num_agents):
-            nmis = min(int(cfg.num_missiles[a]), slots) if slots == 4 else slots
-            for k in range(nmis):
-                m = self.get_missile(env, a, k)
-                if m[0] < 0:
-                    self._acmi_exploded.discard((a, k))
-                    continue
-                flying.append((0.0, a, k, m, nmis))
-        for _, a, k, _m, _n in flying:
-            self._acmi_first.setdefault((a, k), (step, a))      # dict position of the uid: its first launch (step, agent order)
-        flying.sort(key=lambda r: self._acmi_first[(r[1], r[2])])
-        for _, a, k, m, nmis in flying:
-            uid = f"{uids[a]}{nmis - k}"
-            rec, boom = acmi.missile_records(uid, color(a), int(m[0]), m[1:4], m[7], m[8], center, (a, k) in self._acmi_exploded,
-                                             300 if base_missile else 5, acmi.MISSILE_MODELS[int(m[11])])
-            if boom:
-                self._acmi_exploded.add((a, k))
-            msgs.append(rec)
-        # env._chaffsims: one ChaffSimulator per qualifying incoming missile of a release event, uid "agent + (remaining + 10)"
-        if cfg.task in (AC_TASK_SCENARIO1, AC_TASK_SCENARIO_NVN):
+            ms = [self.get_missile(env, a, k) for k in range(w.n_slots[a])]
+            slots.append([(m[0], m[11], m[1], m[2], m[3], m[7], m[8]) for m in ms])
+        chaff = None
+        if w.has_chaff:
+            chaff = []
             for a in range(self.num_agents):
                 st = self.get_state(env, a)
-                n_ch = int(st[self._ix("x_n_ch")])
-                rem = int(cfg.num_missiles[a])
-                for q in range(min(n_ch, 2)):
-                    mult = int(st[self._ix(f"x_ch_mult{q}")])
-                    alive = int(st[self._ix(f"x_ch_status{q}")]) == 0
-                    for j in range(mult):
-                        uid = f"{uids[a]}{rem + 10}"
-                        rem -= 1
-                        if uid not in self._acmi_chaff:
-                            self._acmi_chaff[uid] = {"color": color(a), "pose": tuple(entities[a][:6])}
-                        self._acmi_chaff[uid]["alive"] = alive
-            for uid, ch in self._acmi_chaff.items():
-                msgs.append(acmi.chaff_record(uid, ch["color"], ch["alive"], ch["pose"]))
+                chaff.append((int(st[self._ix("x_n_ch")]),
+                              tuple((int(st[self._ix(f"x_ch_status{q}")]), int(st[self._ix(f"x_ch_mult{q}")])) for q in range(2))))
         with open(filepath, mode="a", encoding="utf-8-sig") as f:
-            f.write(f"#{step * cfg.agent_interaction_steps / cfg.sim_freq:.2f}\n")
-            for msg in msgs:
-                f.write(msg + "\n")
+            f.write(w.frame(step, entities, slots, chaff))
+
+    def record(self, envs=None, frames=1024):
+        """Create a ``FlightRecorder`` (recorder.py) for env indices ``envs`` (None: all) with room for ``frames`` frames, and attach it:
+        from now on one small kernel behind every step this handle takes -- ``step``, ``step_device``, and the steps that
+        ``DeviceRollout.collect``, ``DeviceMAPPORollout.collect`` and ``DeviceEvaluator.run`` queue from C++ -- and behind ``reset()``
+        appends what an ACMI frame needs to the recorder's ring in device memory. One recorder is attached at a time; while one is,
+        host steps are dispatched as HIP launches instead of AQL packets."""
+        from .recorder import FlightRecorder
+        self._assert_not_closed()
+        rec = FlightRecorder(self, envs=envs, frames=frames)
+        try:
+            rec.attach()
+        except Exception:
+            rec.close()
+            raise
+        return rec
+
+    def stop_recording(self):
+        """Detach the attached recorder (nothing attached: nothing happens). Its frames stay readable until it is closed."""
+        self._assert_not_closed()
+        self.lib.check(self.lib.ac_recorder_detach(self._h), "ac_recorder_detach")
+        self._recorder = None
+
+    @property
+    def recorder(self):
+        """the attached ``FlightRecorder``, or None"""
+        return getattr(self, "_recorder", None)
 
     def _ix(self, name):
         if not hasattr(self, "_names"):
@@ -474,6 +460,11 @@ class HipVecEnv:
         handle first and freed when the last of them is gone."""
         if self.closed:
             return
+        for ref in list(getattr(self, "_recorders", [])):      # flight recorders hold device memory that belongs with the handle
+            rec = ref()
+            if rec is not None:
+                rec.close()
+        self._recorder = None
         if self.copy:
             for st in self._sets:
                 if self._held(st):
