@@ -4,6 +4,8 @@ Mirrors ``parse_config`` (reference envs/JSBSim/utils/utils.py:7-23) and the ``g
 convention of the reward / termination classes (reward_function_base.py:14-15, altitude_reward.py:14-16, low_altitude.py:13,
 overload.py:18-20, timeout.py:16), for the tasks the HIP path implements.
 """
+import math
+
 import yaml
 
 from .capi import (AcConfig, AC_MAX_AGENTS, AC_TASK_HEADING, AC_TASK_SINGLECOMBAT, AC_TASK_DODGE_MISSILE, AC_TASK_WVR, AC_TASK_MANEUVER,
@@ -150,6 +152,8 @@ def config_from_dict(data, task=None, hierarchical=None):
     cfg.max_steps = int(data.get("max_steps", 100))                              # env_base.py:25
     lon, lat, alt = data.get("battle_field_center", (120.0, 60.0, 0.0))
     cfg.center_lon, cfg.center_lat, cfg.center_alt = float(lon), float(lat), float(alt)
+    if not all(math.isfinite(v) for v in (cfg.center_lon, cfg.center_lat, cfg.center_alt)) or abs(cfg.center_lat) > 90.0:
+        raise ValueError(f"battle_field_center {[lon, lat, alt]} must be finite, with a latitude in [-90, 90]")
     cfg.altitude_limit = float(data.get("altitude_limit", 2500))
     cfg.acc_limit_x = float(data.get("acceleration_limit_x", 10.0))
     cfg.acc_limit_y = float(data.get("acceleration_limit_y", 10.0))
@@ -162,6 +166,13 @@ def config_from_dict(data, task=None, hierarchical=None):
         # catalogue bounds applied by set_property_value (catalog.py:237,247)
         ic["h_sl_ft"] = _clip(ic["h_sl_ft"], -1400, 85000)
         ic["psi_deg"] = _clip(ic["psi_deg"], 0, 360)
+        # what the kernels cannot represent is refused here as ac_create refuses it: a non-finite value, and a latitude within a
+        # degree of a pole (the local frame divides by the distance from the polar axis)
+        for k, v in ic.items():
+            if not math.isfinite(v):
+                raise ValueError(f"{uid}: init_state {k} = {v} is not finite")
+        if abs(ic["lat_geod_deg"]) > 89.0:
+            raise ValueError(f"{uid}: initial latitude {ic['lat_geod_deg']} is beyond 89 deg: the local frame is not defined on a pole")
         for k, v in ic.items():
             setattr(cfg.init[i], k, v)
         cfg.num_missiles[i] = int(acs[uid].get("missile", 0))

@@ -2001,6 +2001,20 @@ int ac_create(const ac_config_t* cfg, int32_t n_envs, int32_t device_id, uint64_
   if (cfg->sim_freq != 60) return fail("ac_create: sim_freq must be 60 (the FDM tick is compiled for 1/60 s)");
   for (int i = 0; i < cfg->n_agents; ++i)
     if (cfg->num_missiles[i] < 0 || cfg->num_missiles[i] > AC_MAX_MISSILES_PER_AGENT) return fail("ac_create: num_missiles out of range");
+  // initial conditions the kernels cannot represent: the local frame takes the direction of the polar axis distance by rsqrt(x^2 + y^2)
+  // in fp32 (f16::locate_fast), which is 0 on a pole; the atmosphere has the three layers below 85 000 ft (the catalogue's own bound)
+  if (!std::isfinite(cfg->center_lon) || !std::isfinite(cfg->center_lat) || !std::isfinite(cfg->center_alt) || fabs(cfg->center_lat) > 90.0)
+    return fail("ac_create: battle_field_center must be finite, with a latitude in [-90, 90]");
+  for (int i = 0; i < cfg->n_agents; ++i) {
+    const ac_init_state_t& ic = cfg->init[i];
+    const double v[10] = {ic.lon_deg, ic.lat_geod_deg, ic.h_sl_ft, ic.psi_deg, ic.u_fps, ic.v_fps, ic.w_fps, ic.p_rad_sec, ic.q_rad_sec, ic.r_rad_sec};
+    for (double x : v)
+      if (!std::isfinite(x)) return fail("ac_create: non-finite initial condition (init[" + std::to_string(i) + "])");
+    if (fabs(ic.lat_geod_deg) > 89.0)
+      return fail("ac_create: initial latitude beyond 89 deg (init[" + std::to_string(i) + "]): the local frame is not defined on a pole");
+    if (ic.h_sl_ft < -1400.0 || ic.h_sl_ft > 85000.0)
+      return fail("ac_create: initial altitude outside -1400 .. 85000 ft (init[" + std::to_string(i) + "]): the catalogue's bounds of ic/h-sl-ft");
+  }
   int ndev = 0;
   HIP_OK(hipGetDeviceCount(&ndev));
   if (device_id < 0 || device_id >= ndev) return fail("ac_create: no such HIP device");
