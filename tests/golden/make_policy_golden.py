@@ -14,6 +14,12 @@ actions (int8), log-probs (float64), new GRU states (float32), each head's logit
 the seeded case the values (float64) and the critic's new state (float32). Only data is stored; no reference source text.
 
     python tests/golden/make_policy_golden.py
+
+policy_edges.npz (``python tests/golden/make_policy_golden.py edges`` writes it alone) pins the restatement at every configuration of
+tests/policy_edges_util.py's table: the first 32 rows of the reference's PPOActor / PPOCritic in float64 on the table's hashed weights
+and inputs, keys ``<entry>/<array>``: actions (uint8: a head may have 160 categories), log_probs, values, shoot_p (float64), logits, rnn_states_out,
+rnn_states_critic_out (float32). The wide entries' critic is the reference's PPOCritic on cent_obs. Nothing else is stored: weights
+and inputs come from the hash.
 """
 import os
 import sys
@@ -161,5 +167,41 @@ def main():
         print(f"wrote {out}: {len(data)} arrays, {os.path.getsize(out)} bytes")
 
 
+def edges():
+    sp = stub_gymnasium()
+    from algorithms.ppo.ppo_actor import PPOActor
+    from algorithms.ppo.ppo_critic import PPOCritic
+    import policy_edges_util as E
+
+    data, R = {}, E.GOLDEN_ROWS
+    for name, e in E.ENTRIES.items():
+        d = E.inputs(name)
+        space = sp.MultiDiscrete(e.nvec)
+        act_space = sp.Tuple([space, sp.MultiDiscrete([2] * e.n_shoot)]) if e.n_shoot else space
+        args = args_ns(use_prior=e.n_shoot > 0, use_feature_normalization=e.fn)
+        actor = PPOActor(args, sp.Box(low=-10, high=10.0, shape=(e.obs_dim,)), act_space)
+        actor.load_state_dict({k: torch.from_numpy(np.array(v)) for k, v in d["sd"].items()})
+        crit = PPOCritic(args, sp.Box(low=-10, high=10.0, shape=(E.critic_dim(e),)))
+        crit.load_state_dict({k: torch.from_numpy(np.array(v)) for k, v in d["critic_sd"].items()})
+        for m in (actor, crit):
+            m.double()
+            m.tpdv = dict(dtype=torch.float64, device=torch.device("cpu"))
+        t64 = lambda x: torch.from_numpy(np.asarray(x[:R], dtype=np.float64))
+        obs64, m64 = t64(d["obs"]), t64(d["masks"])
+        with torch.no_grad():
+            act, logp, h = actor(obs64, t64(d["rnn_states"]), m64, deterministic=True)
+            val, hc = crit(t64(E.critic_input(e, d)), t64(d["rnn_states_critic"]), m64)
+        det = head_details(actor, obs64, t64(d["rnn_states"]), m64, len(e.nvec), e.n_shoot)
+        data[f"{name}/actions"], data[f"{name}/log_probs"], data[f"{name}/values"] = act.numpy().astype(np.uint8), logp.numpy(), val.numpy()
+        data[f"{name}/logits"] = det["logits"].astype(np.float32)
+        data[f"{name}/rnn_states_out"], data[f"{name}/rnn_states_critic_out"] = h.numpy().astype(np.float32), hc.numpy().astype(np.float32)
+        if e.n_shoot:
+            data[f"{name}/shoot_p"] = det["shoot_p"]
+    np.savez_compressed(E.GOLDEN, **data)
+    print(f"wrote {E.GOLDEN}: {len(data)} arrays, {os.path.getsize(E.GOLDEN)} bytes")
+
+
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] != ["edges"]:
+        main()
+    edges()

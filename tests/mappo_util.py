@@ -31,12 +31,7 @@ def seeded_state_dicts(tag):
     critic = U.seeded_state_dicts(cent, nvec, fn, seed=seed)[1]
     if tag == "d":
         return None, critic
-    actor = U.seeded_state_dicts(obs_dim, nvec, fn, seed=seed)[0]
-    b = np.float32(1.0 / np.sqrt(128))
-    for s in range(n_shoot):
-        k = len(nvec) + s
-        actor[f"act.action_outs.{k}.net.weight"] = (U.hashed(seed * 1000 + 300 + s, 2 * 128) * b).reshape(2, 128)
-        actor[f"act.action_outs.{k}.net.bias"] = U.hashed(seed * 1000 + 400 + s, 2) * b
+    actor = U.add_munition_heads(U.seeded_state_dicts(obs_dim, nvec, fn, seed=seed)[0], len(nvec), n_shoot, seed)
     return actor, critic
 
 

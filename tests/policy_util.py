@@ -4,6 +4,7 @@ pinned to the reference's own modules by the golden fixtures (test_policy_host.p
 The fixtures hold what cannot be recomputed without the reference: its outputs, the inputs drawn for them, and the shipped 1v1 actor.
 The seeded case's weights and every case's GRU-state inputs come from `hashed`, an exact integer hash that make_policy_golden.py and
 the tests evaluate alike, so they are not stored."""
+import contextlib
 import os
 import types
 
@@ -67,6 +68,17 @@ def seeded_state_dicts(obs_dim, nvec, use_fn, seed=SEED_WEIGHTS):
     return a, c
 
 
+def add_munition_heads(actor_sd, n_cat, n_shoot, seed):
+    """The munition heads act.action_outs.{n_cat + s}.net, Linear(128, 2), added to a seeded actor state_dict from the same hash (the
+    one recipe of the MAPPO goldens, the pool members and the edge configurations)."""
+    b = np.float32(1.0 / np.sqrt(128))
+    for s in range(n_shoot):
+        k = n_cat + s
+        actor_sd[f"act.action_outs.{k}.net.weight"] = (hashed(seed * 1000 + 300 + s, 2 * 128) * b).reshape(2, 128)
+        actor_sd[f"act.action_outs.{k}.net.bias"] = hashed(seed * 1000 + 400 + s, 2) * b
+    return actor_sd
+
+
 def golden_case(tag):
     """One case as a dict: the stored arrays plus the generated ones (GRU-state inputs, the seeded weights as ``sd`` / ``critic_sd``,
     ``probs`` = the softmax of each head's stored logits)."""
@@ -116,8 +128,21 @@ def args(tag):
                                  activation_id=1, use_feature_normalization=fn, use_prior=prior, use_recurrent_policy=True)
 
 
+DTYPE = torch.float64   # the restatement's precision; `precision(torch.float32)` runs it as the float32 eager twin
+
+
+@contextlib.contextmanager
+def precision(dtype):
+    global DTYPE
+    old, DTYPE = DTYPE, dtype
+    try:
+        yield
+    finally:
+        DTYPE = old
+
+
 def _t(x):
-    return torch.as_tensor(np.asarray(x, dtype=np.float64))
+    return torch.as_tensor(np.asarray(x, dtype=np.float64)).to(DTYPE)
 
 
 def _mlp(sd, prefix, x):
@@ -146,8 +171,8 @@ def _trunk(sd, obs, rnn, masks, use_fn):
 def prior(obs):
     o = _t(obs)
     ang, dist = torch.rad2deg(o[:, 11]), o[:, 13] * 10000
-    a0 = torch.full((o.shape[0],), 3.0, dtype=torch.float64)
-    b0 = torch.full((o.shape[0],), 10.0, dtype=torch.float64)
+    a0 = torch.full((o.shape[0],), 3.0, dtype=DTYPE)
+    b0 = torch.full((o.shape[0],), 10.0, dtype=DTYPE)
     a0[dist <= 12000] = 6
     a0[dist <= 8000] = 10
     b0[ang <= 45] = 6

@@ -28,13 +28,7 @@ def args(fn, prior):
 
 def member_sd(obs_dim, nvec, n_shoot, fn, seed):
     """policy_util's seeded actor (one hash stream per tensor), plus munition heads when the action space has them."""
-    a = U.seeded_state_dicts(obs_dim, nvec, fn, seed=seed)[0]
-    b = np.float32(1.0 / np.sqrt(128))
-    for s in range(n_shoot):
-        k = len(nvec) + s
-        a[f"act.action_outs.{k}.net.weight"] = (U.hashed(seed * 1000 + 300 + s, 256) * b).reshape(2, 128)
-        a[f"act.action_outs.{k}.net.bias"] = U.hashed(seed * 1000 + 400 + s, 2) * b
-    return a
+    return U.add_munition_heads(U.seeded_state_dicts(obs_dim, nvec, fn, seed=seed)[0], len(nvec), n_shoot, seed)
 
 
 def heads(act_space):
