@@ -2847,6 +2847,6 @@ int ac_get_missile_target(ac_env_t* h, int32_t env, int32_t agent, int32_t k, in
 #include "mlp_train.hpp"
 #include "act_train.hpp"
 #include "ppo_update.hpp"
+#include "collect_common.hpp"
 #include "rollout_collect.hpp"
-#include "rollout_share_collect.hpp"
 #include "eval_collect.hpp"

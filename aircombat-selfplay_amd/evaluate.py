@@ -21,9 +21,9 @@ import ctypes as C
 
 import numpy as np
 
-from .capi import AcEvalConfig, AcEvalState, AC_EVAL_NO_OPPONENT, AC_EVAL_OPPONENT_POLICY, AC_EVAL_OPPONENT_POOL
-from .policy import DevicePolicy, DevicePolicyPool, HID
-from .rollout import device_view, stream_of
+from .capi import AcEvalConfig, AcEvalState
+from .policy import DevicePolicyPool, HID
+from .rollout import device_view, opponent_kind, stream_of
 
 _U64 = 2 ** 64 - 1
 
@@ -138,16 +138,8 @@ class DeviceEvaluator:
     def __init__(self, envs, policy, opponent=None, num_learner_agents=None, episodes_per_env=1, deterministic=True, opponent_deterministic=True):
         self.lib = envs.lib
         self.envs, self.policy, self.opponent = envs, policy, opponent
-        if opponent is None:
-            kind = AC_EVAL_NO_OPPONENT
-        elif isinstance(opponent, DevicePolicyPool):
-            kind = AC_EVAL_OPPONENT_POOL
-        elif isinstance(opponent, DevicePolicy):
-            kind = AC_EVAL_OPPONENT_POLICY
-        else:
-            raise TypeError("opponent is None, a DevicePolicy / DeviceMAPPOPolicy (critic=False) or a DevicePolicyPool")
-        A = envs.num_agents
-        self.num_learner_agents = int(num_learner_agents) if num_learner_agents is not None else (A if opponent is None else A // 2)
+        kind, self.num_learner_agents = opponent_kind(opponent, num_learner_agents, envs.num_agents,
+                                                      "a DevicePolicy / DeviceMAPPOPolicy (critic=False) or a DevicePolicyPool")
         self.episodes_per_env = int(episodes_per_env)
         self.device_id = int(policy.device_id)
         cfg = AcEvalConfig(self.num_learner_agents, kind, int(bool(deterministic)), int(bool(opponent_deterministic)), self.episodes_per_env)

@@ -13,7 +13,7 @@ before whatever is queued on either afterwards.
 
 ``DeviceMAPPORollout`` is the same for runner/share_jsbsim_runner.py: a ``HipShareVecEnv`` (or ``HipVecEnv``), a ``DeviceMAPPOPolicy``,
 a ``DeviceSharedReplayBuffer`` and, for self-play, an actor-only ``DeviceMAPPOPolicy`` or a ``DevicePolicyPool(form="mappo")``. Its
-post-step kernel (csrc/rollout_share_collect.hpp) also writes ``share_obs``, ``active_masks`` and the log-probs once per head column;
+post-step kernel (the same file's share form) also writes ``share_obs``, ``active_masks`` and the log-probs once per head column;
 the results are bit for bit those of the stepwise loop of INTEGRATION.md §5e.
 
 Out of scope for both: the per-step ``infos`` history, ``MultiDeviceVecEnv`` (one collector per device) and graph capture; for the
@@ -46,6 +46,23 @@ def stream_of(device_id, stream):
     return stream, stream.cuda_stream
 
 
+def opponent_kind(opponent, num_learner_agents, num_agents, accepted):
+    """(opponent kind of the C ABI, learner agents) for a collector or evaluator: the kind from ``opponent``'s type (the AC_ROLLOUT_* and
+    AC_EVAL_* kinds are the same numbers), the learner's agents defaulting to all of them without an opponent and the first half with
+    one. ``accepted`` words the ``TypeError`` for anything else."""
+    if opponent is None:
+        kind = AC_ROLLOUT_NO_OPPONENT
+    elif isinstance(opponent, DevicePolicyPool):
+        kind = AC_ROLLOUT_OPPONENT_POOL
+    elif isinstance(opponent, DevicePolicy):
+        kind = AC_ROLLOUT_OPPONENT_POLICY
+    else:
+        raise TypeError(f"opponent is None, {accepted}")
+    if num_learner_agents is None:
+        num_learner_agents = num_agents if opponent is None else num_agents // 2
+    return kind, int(num_learner_agents)
+
+
 class DeviceRollout:
     """``DeviceRollout(envs, policy, buffer, opponent=None, num_learner_agents=None)``: the learner ``policy`` owns agents
     ``[0, num_learner_agents)`` of every env (default: all of them without an opponent, the first half with one) and ``buffer`` holds
@@ -63,16 +80,8 @@ class DeviceRollout:
     def __init__(self, envs, policy, buffer, opponent=None, num_learner_agents=None, deterministic=False, opponent_deterministic=False):
         self.lib = envs.lib
         self.envs, self.policy, self.buffer, self.opponent = envs, policy, buffer, opponent
-        if opponent is None:
-            kind = AC_ROLLOUT_NO_OPPONENT
-        elif isinstance(opponent, DevicePolicyPool):
-            kind = AC_ROLLOUT_OPPONENT_POOL
-        elif isinstance(opponent, DevicePolicy):
-            kind = AC_ROLLOUT_OPPONENT_POLICY
-        else:
-            raise TypeError(f"opponent is None, {self._opponent_doc}")
         A = envs.num_agents
-        self.num_learner_agents = int(num_learner_agents) if num_learner_agents is not None else (A if opponent is None else A // 2)
+        kind, self.num_learner_agents = opponent_kind(opponent, num_learner_agents, A, self._opponent_doc)
         self.device_id = int(policy.device_id)
         cfg = AcRolloutConfig(self.num_learner_agents, kind, int(bool(deterministic)), int(bool(opponent_deterministic)))
         h = C.c_void_p()

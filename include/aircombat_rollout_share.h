@@ -5,7 +5,7 @@
  *   R/runner/share_jsbsim_runner.py:157-185 (collect), :196-223 (insert)   (R = the reference repository)
  * is the policy launch, the opponent launch (self-play), the env step and the runner's insert(). ac_share_rollout_collect queues n such
  * steps from C++ with no host work in between; insert() and SharedReplayBuffer.insert (R/algorithms/utils/buffer.py:312-343) are one
- * kernel, the share post-step kernel (csrc/rollout_share_collect.hpp). Same library as aircombat.h (libaircombat_hip.so), same errors:
+ * kernel, the share post-step kernel (csrc/rollout_collect.hpp). Same library as aircombat.h (libaircombat_hip.so), same errors:
  * 0 on success, -1 on failure with the message in ac_last_error(). One caller thread per handle.
  *
  * The learner owns agents [0, na) of every env (na = A, or A / 2 for self-play) and the buffer's N = E * na columns, in (env, agent)

@@ -2,6 +2,7 @@
 were there before it: get_actions on the buffer's slot, the actions written into the env's action buffer, act_into_env for the opponent,
 step_device, the runners' dones_env / zeroing / masks in torch, buffer.insert(on_device=True). Both paths run the same kernels on the
 same inputs, so everything is compared bit for bit."""
+import ctypes as C
 import importlib
 import types
 
@@ -300,13 +301,44 @@ def test_refusals(pkg, P):
             ro.collect(n)
     with pytest.raises(ValueError, match="runs past buffer_size"):
         ro.collect(T + 1)
+    # weights that were never loaded: refused by the loop the two rollout forms and the evaluator share, before anything is queued
+    unloaded = make((P.DevicePolicy, (env.observation_space, env.action_space, a)))
+    ro_unloaded = make((DR, (env, unloaded, buf)), opponent=opp)
+    with pytest.raises(ValueError, match="learner's weights are not loaded"):
+        ro_unloaded.collect(1)
+    assert buf.step == 0 and unloaded.counter == 0 and opp.counter == 70
+    unloaded_opp = make((P.DevicePolicy, (env.observation_space, env.action_space, a)), critic=False)
+    ro_unloaded_opp = make((DR, (env, pol, buf)), opponent=unloaded_opp)
+    with pytest.raises(ValueError, match="opponent's weights are not loaded"):
+        ro_unloaded_opp.collect(1)
+    assert buf.step == 0 and pol.counter == 40 and unloaded_opp.counter == 0
     assert_same(s.result(False), before)                 # nothing moved: buffer, env, counters
+    # a hierarchical env whose controller was never loaded (HipVecEnv always loads it: the handle is made through the C ABI)
+    hcfg = pkg.default_config("hierarchical_multiplecombat")
+    hh = C.c_void_p()
+    env.lib.check(env.lib.ac_create(C.byref(hcfg), E, 0, 7, C.byref(hh)), "ac_create")
+    hD, hA = env.lib.ac_obs_dim(hh), int(hcfg.n_agents)
+    bare = types.SimpleNamespace(lib=env.lib, _h=hh, num_agents=hA, num_envs=E)
+    h_obs, h_act = ve._Box(-10, 10, (hD,)), ve._MultiDiscrete([3, 5, 3])
+    hpol = make((P.DevicePolicy, (h_obs, h_act, a)))
+    hpol.load_state_dict(*state_dicts(hD, [3, 5, 3], 0, True, 1203))
+    hbuf = make((pkg.DeviceReplayBuffer, (a, hA, h_obs, h_act)))
+    hro = make((DR, (bare, hpol, hbuf)))
+    hbefore = {k: hbuf.array(k) for k in FIELDS}
+    with pytest.raises(ValueError, match="ac_load_controller has not been called"):
+        hro.collect(1)
+    torch.cuda.synchronize()
+    assert hbuf.step == 0 and hpol.counter == 0
+    for k in FIELDS:
+        assert np.array_equal(bits(hbuf.array(k)), bits(hbefore[k])), k
+    hro.close()
+    env.lib.ac_destroy(hh)
     ro.collect(T - 2)
     mid = s.result(False)
     with pytest.raises(ValueError, match="runs past buffer_size"):
         ro.collect(3)
     assert_same(s.result(False), mid)
     assert s.buffer.step == T - 2 and s.policy.counter == 40 + T - 2 and s.opp.counter == 70 + T - 2
-    for x in made:
+    for x in reversed(made):
         x.close()
     s.close()

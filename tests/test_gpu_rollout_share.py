@@ -1,4 +1,4 @@
-"""DeviceMAPPORollout.collect (csrc/rollout_share_collect.hpp) on the MI355X against the stepwise loop it replaces,
+"""DeviceMAPPORollout.collect (csrc/rollout_collect.hpp) on the MI355X against the stepwise loop it replaces,
 built only from the calls that were there before it: get_actions on the buffer's slots (share_obs, obs), the actions written into the
 env's action buffer, act_into_env for the opponent, step_device, the share runner's dones_env / zeroing / masks / active_masks and
 share_obs in torch, buffer.insert(on_device=True) with the log-probs expanded to act_dim. Both paths run the same kernels on the same

@@ -1,5 +1,5 @@
 """The MAPPO rollout collector without a GPU: the share post-step kernel's row function (ac_share_rollout_post_step_host,
-csrc/rollout_share_collect.hpp) against a numpy restatement, in this project's own words, of what the share runner's insert()
+csrc/rollout_collect.hpp) against a numpy restatement, in this project's own words, of what the share runner's insert()
 (runner/share_jsbsim_runner.py:196-223) followed by SharedReplayBuffer.insert (algorithms/utils/buffer.py:312-343) leave behind, bit for
 bit; the new header against its ctypes mirror; the exports."""
 import ctypes as C
@@ -109,6 +109,47 @@ def test_row_function_matches_the_share_runners_insert(pkg, E, A, na, D, pattern
         if opp:
             for k in want_opp:
                 assert np.array_equal(got_opp[k].view(np.uint32), want_opp[k].view(np.uint32)), (k, s)
+
+
+@pytest.mark.parametrize("pattern", PATTERNS)
+@pytest.mark.parametrize("E,A,na,D", [sh for sh in SHAPES if sh[3] == 15])
+def test_both_forms_write_the_common_arrays_alike(pkg, E, A, na, D, pattern):
+    """The PPO form's row function (ac_rollout_post_step_host) and the share form's are one template: on the same env-side arrays and
+    the same initial buffer contents, every array both forms have ends up byte for byte the same, at every slot."""
+    lib = pkg.load_library()
+    capi = pkg.capi
+    rng = np.random.default_rng(2000 * E + 100 * A + 10 * na + D)
+    f = lambda *shape: rng.normal(0, 1, shape).astype(np.float32)
+    common = ("obs", "rewards", "actions", "masks", "rnn_states_actor", "rnn_states_critic")
+    ptr = lambda a: a.ctypes.data
+    for s in range(T):
+        buf = {"obs": f(T + 1, E, na, D), "share_obs": f(T + 1, E, na, A * D), "actions": f(T, E, na, BUF_ACT), "rewards": f(T, E, na, 1),
+               "masks": f(T + 1, E, na, 1), "active_masks": f(T + 1, E, na, 1), "action_log_probs": f(T, E, na, BUF_ACT),
+               "rnn_states_actor": f(T + 1, E, na, 1, HID), "rnn_states_critic": f(T + 1, E, na, 1, HID)}
+        opp = {"h": f(E, A - na, 1, HID), "masks": f(E, A - na, 1)} if na < A else None
+        obs, actions, rewards, logp = f(E, A, D), f(E, A, ENV_ACT), f(E, A, 1), f(E, na, 1)
+        d8 = np.ascontiguousarray(dones_for(pattern, E, A, rng).astype(np.uint8))
+        ppo, share = ({k: v.copy() for k, v in buf.items()} for _ in range(2))
+        ppo_opp, share_opp = ({k: v.copy() for k, v in opp.items()} if opp else None for _ in range(2))
+        opp_ptrs = lambda o: (ptr(o["h"]), ptr(o["masks"])) if o else (None, None)
+        st = capi.AcRolloutPostStep(E, A, na, D, ENV_ACT, BUF_ACT, HID, T, s, ptr(obs), ptr(rewards), ptr(actions), ptr(d8),
+                                    ptr(ppo["obs"]), ptr(ppo["rewards"]), ptr(ppo["actions"]), ptr(ppo["masks"]),
+                                    ptr(ppo["rnn_states_actor"]), ptr(ppo["rnn_states_critic"]), *opp_ptrs(ppo_opp))
+        assert lib.ac_rollout_post_step_host(C.byref(st)) == 0, lib.last_error()
+        st = capi.AcShareRolloutPostStep(E, A, na, D, ENV_ACT, BUF_ACT, HID, T, s, ptr(obs), ptr(rewards), ptr(actions), ptr(d8), ptr(logp),
+                                         ptr(share["obs"]), ptr(share["share_obs"]), ptr(share["rewards"]), ptr(share["actions"]),
+                                         ptr(share["action_log_probs"]), ptr(share["masks"]), ptr(share["active_masks"]),
+                                         ptr(share["rnn_states_actor"]), ptr(share["rnn_states_critic"]), *opp_ptrs(share_opp))
+        assert lib.ac_share_rollout_post_step_host(C.byref(st)) == 0, lib.last_error()
+        for k in common:
+            assert ppo[k].tobytes() == share[k].tobytes(), (k, s)
+            if not k.startswith("rnn_"):                                # (and the step did write them; the states only where done)
+                assert ppo[k].tobytes() != buf[k].tobytes(), (k, s)
+        for k in ("share_obs", "active_masks", "action_log_probs"):     # the PPO form has no pointer to these
+            assert ppo[k].tobytes() == buf[k].tobytes(), (k, s)
+        if opp:
+            for k in opp:
+                assert ppo_opp[k].tobytes() == share_opp[k].tobytes(), (k, s)
 
 
 def test_row_function_refusals(pkg):
