@@ -7,7 +7,7 @@ The directory name carries a hyphen, so import it as ``importlib.import_module("
 or through the repo-root alias module ``aircombat_selfplay_amd``.
 """
 from .capi import AcConfig, AcInitState, Lib, load_library, library_path, HipExtensionMissing  # noqa: F401
-from .config import config_from_yaml, default_config, default_nvn_config, TASK_IDS  # noqa: F401
+from .config import config_from_yaml, default_config, default_nvn_config, curriculum_bank, TASK_IDS  # noqa: F401
 from .vec_env import HipVecEnv, HipShareVecEnv, MultiDeviceVecEnv, make_env, controller_forward  # noqa: F401
 from .rollout_buffer import DeviceReplayBuffer, DeviceSharedReplayBuffer  # noqa: F401
 from .snapshot import EnvSnapshot, MultiSnapshot, SnapshotMismatch  # noqa: F401
@@ -15,6 +15,7 @@ from .policy import DevicePolicy, DeviceMAPPOPolicy, DevicePolicyPool, Unsupport
 from .rollout import DeviceRollout, DeviceMAPPORollout  # noqa: F401
 from .evaluate import DeviceEvaluator, EvalResult, elo_update  # noqa: F401
 from .recorder import FlightRecorder  # noqa: F401
+from .spawn import SpawnCurriculum  # noqa: F401
 from . import sharding  # noqa: F401
 
 _TORCH_EXPORTS = {"DeviceGRUFunction": "gru_train", "DeviceGRULayer": "gru_train", "use_device_gru": "gru_train",
@@ -33,7 +34,7 @@ def __getattr__(name):
 __all__ = ["AcConfig", "AcInitState", "Lib", "load_library", "library_path", "HipExtensionMissing",
            "config_from_yaml", "default_config", "default_nvn_config", "TASK_IDS", "HipVecEnv", "HipShareVecEnv", "MultiDeviceVecEnv", "make_env", "controller_forward",
            "DeviceReplayBuffer", "DeviceSharedReplayBuffer", "EnvSnapshot", "MultiSnapshot", "SnapshotMismatch",
-           "DevicePolicy", "DeviceMAPPOPolicy", "DevicePolicyPool", "UnsupportedPolicy", "DeviceRollout", "DeviceMAPPORollout", "DeviceEvaluator", "EvalResult", "elo_update", "FlightRecorder", "DeviceGRUFunction", "DeviceGRULayer", "use_device_gru",
+           "DevicePolicy", "DeviceMAPPOPolicy", "DevicePolicyPool", "UnsupportedPolicy", "DeviceRollout", "DeviceMAPPORollout", "DeviceEvaluator", "EvalResult", "elo_update", "FlightRecorder", "SpawnCurriculum", "curriculum_bank", "DeviceGRUFunction", "DeviceGRULayer", "use_device_gru",
            "DeviceMLPBlockFunction", "DeviceMLPLayer", "mlp_block", "use_device_mlp",
            "DeviceActEvalFunction", "act_evaluate", "use_device_act",
            "DevicePPOLossFunction", "ppo_loss", "device_clip_adam_step", "DevicePPOTrainer"]

@@ -144,6 +144,29 @@ class AcRecorderInfo(C.Structure):
 
 AC_REC_DONE, AC_REC_AFTER_RESET = 1, 2
 
+
+# ---- include/aircombat_spawn.h
+AC_SPAWN_FIXED, AC_SPAWN_AUTO = 0, 1
+AC_SPAWN_AT, AC_SPAWN_UPTO = 0, 1
+AC_SPAWN_MAX_BANK, AC_SPAWN_MAX_WINDOW = 1024, 32
+
+
+class AcSpawnConfig(C.Structure):
+    """ac_spawn_config_t: the spawn curriculum's mode, rule and sampling."""
+    _fields_ = [(n, C.c_int32) for n in ("mode", "sample", "window", "min_wins")] + [("win_return", C.c_float), ("pad_", C.c_int32), ("seed", C.c_uint64)]
+
+
+class AcSpawnState(C.Structure):
+    """ac_spawn_state_t: device pointers of the per-env arrays."""
+    _fields_ = [("E", C.c_int32), ("K", C.c_int32)] + \
+               [(n, C.c_void_p) for n in ("stage", "spawned", "episode", "ret_acc", "wins", "played", "return_sum")]
+
+
+class AcSpawnPostStep(C.Structure):
+    """ac_spawn_post_step_t: one step of the rule on host arrays (ac_spawn_post_step_host)."""
+    _fields_ = [(n, C.c_int32) for n in ("E", "A", "n_ego", "K", "all_envs", "pad_")] + [("cfg", AcSpawnConfig)] + \
+               [(n, C.c_void_p) for n in ("rewards", "info", "stage", "spawned", "episode", "ret_acc", "wins", "played", "return_sum", "index")]
+
 AC_PPO_STAT_LOSS, AC_PPO_STAT_POLICY_LOSS, AC_PPO_STAT_VALUE_LOSS, AC_PPO_STAT_ENTROPY_LOSS, AC_PPO_STAT_RATIO_MEAN, AC_PPO_STAT_DENOMINATOR = range(6)
 AC_PPO_NSTAT = 8
 
@@ -296,6 +319,14 @@ SIGNATURES = {
     "ac_recorder_info": (C.c_int, [_p, C.POINTER(AcRecorderInfo)]),
     "ac_recorder_read": (C.c_int, [_p, C.c_int32, C.c_int64, C.c_int32, _p]),
     "ac_recorder_device_ptr": (C.c_int, [_p, C.c_int32, C.POINTER(_p), C.POINTER(C.c_int64)]),
+    # include/aircombat_spawn.h
+    "ac_spawn_check": (C.c_int, [C.c_int32, C.c_int32, _p, C.c_int32, _p]),
+    "ac_spawn_attach": (C.c_int, [_p, _p, C.c_int32, _p, C.POINTER(_p)]),
+    "ac_spawn_detach": (C.c_int, [_p]),
+    "ac_spawn_set_config": (C.c_int, [_p, _p]),
+    "ac_spawn_state": (C.c_int, [_p, _p]),
+    "ac_spawn_post_step_host": (C.c_int, [_p]),
+    "ac_spawn_draw_host": (C.c_int, [C.c_uint64, C.c_int64, C.c_int64, C.c_int32, C.POINTER(C.c_int32)]),
 }
 
 

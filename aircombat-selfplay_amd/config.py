@@ -8,7 +8,7 @@ import math
 
 import yaml
 
-from .capi import (AcConfig, AC_MAX_AGENTS, AC_TASK_HEADING, AC_TASK_SINGLECOMBAT, AC_TASK_DODGE_MISSILE, AC_TASK_WVR, AC_TASK_MANEUVER,
+from .capi import (AcConfig, AcInitState, AC_MAX_AGENTS, AC_TASK_HEADING, AC_TASK_SINGLECOMBAT, AC_TASK_DODGE_MISSILE, AC_TASK_WVR, AC_TASK_MANEUVER,
                    AC_TASK_SHOOT_MISSILE, AC_TASK_MULTICOMBAT, AC_TASK_SCENARIO1, AC_TASK_SCENARIO_NVN)
 
 TASK_IDS = {
@@ -99,6 +99,33 @@ def apply_curriculum_spawn(cfg, angle=0):
         put(2, 60.1, 120.0, 0)
         put(3, 60.1, 120.01, 0)
     return cfg
+
+
+def curriculum_bank(cfg, angles=range(181)):
+    """The spawn bank of the reference's curriculum for ``cfg``: one row of ``cfg.n_agents`` ``AcInitState`` per angle, ``cfg.init``
+    with ``apply_curriculum_spawn(angle)`` on top (for two aircraft entry 0 moves; otherwise entries 0-3 are rewritten, as
+    multiplecombat_env.py does). ``cfg`` itself is left alone. Feed it to ``HipVecEnv.spawn_curriculum(init_states=...)``."""
+    rows = []
+    for angle in angles:
+        c = AcConfig.from_buffer_copy(cfg)
+        apply_curriculum_spawn(c, angle)
+        rows.append([AcInitState.from_buffer_copy(c.init[i]) for i in range(cfg.n_agents)])
+    return rows
+
+
+def init_state_from_dict(d):
+    """An ``AcInitState`` from a YAML ``init_state`` block (keys ``ic_*``), with the defaults and catalogue bounds config_from_dict applies."""
+    ic = dict(_IC_DEFAULT)
+    for k, v in (d or {}).items():
+        if k not in _IC_KEYS:
+            raise ValueError(f"unknown init_state key {k!r} (known: {sorted(_IC_KEYS)})")
+        ic[_IC_KEYS[k]] = float(v)
+    ic["h_sl_ft"] = _clip(ic["h_sl_ft"], -1400, 85000)
+    ic["psi_deg"] = _clip(ic["psi_deg"], 0, 360)
+    out = AcInitState()
+    for k, v in ic.items():
+        setattr(out, k, v)
+    return out
 
 # defaults of AircraftSimulator.clear_defalut_condition (simulatior.py:192-208)
 _IC_DEFAULT = dict(lon_deg=120.0, lat_geod_deg=60.0, h_sl_ft=20000.0, psi_deg=0.0, u_fps=800.0, v_fps=0.0, w_fps=0.0,

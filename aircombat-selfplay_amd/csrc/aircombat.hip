@@ -1701,6 +1701,7 @@ static uint64_t fnv1a(uint64_t hsh, const void* p, size_t n) {
 #include "aql_dispatch.hpp"
 
 struct ac_recorder;
+struct ac_spawn;
 struct ac_env {
   ac_config_t cfg;
   DevCfg dc;
@@ -1743,6 +1744,7 @@ struct ac_env {
   AqlState aql;
   bool stream_dirty;                     // work enqueued on `stream` since it was last synchronised: the next AQL dispatch synchronises it
   ac_recorder* rec;                      // the attached flight recorder (flight_recorder.hpp), captured behind every step and reset; null: none
+  ac_spawn* spawn;                       // the attached spawn bank (spawn_bank.hpp), applied behind every step and reset, ahead of the recorder; null: none
 };
 
 static void geodetic2ecef_m(double lat_deg, double lon_deg, double alt, double* x, double* y, double* z) {
@@ -1869,10 +1871,12 @@ static int launch_plan(ac_env* h, const StepPlan& sp) {   // through HIP, on the
   return 0;
 }
 static int recorder_hook(ac_env* h, int after_reset);   // flight_recorder.hpp: one frame of the attached recorder, if there is one
+static int spawn_hook(ac_env* h, int all, int host_set);   // spawn_bank.hpp: the envs that were just reset respawn from the attached bank, if there is one
 static int launch_step(ac_env* h, const float* d_actions, int host_set = -1) {
   StepPlan sp;
   if (step_plan(h, d_actions, host_set, &sp)) return -1;
   if (launch_plan(h, sp)) return -1;
+  if (h->spawn && spawn_hook(h, 0, host_set)) return -1;
   return h->rec ? recorder_hook(h, 0) : 0;
 }
 // ---- the two directions of ordering between the handle's HIP stream and its AQL queue (aql_dispatch.hpp)
@@ -1901,13 +1905,13 @@ static int host_entry(ac_env* h) {
 }
 // A host step: through the AQL queue once it is set up (and no timing bracket is open: bench.py times host steps with HIP events on the
 // stream), else through HIP; the first host step of a handle goes through HIP and sets the queue up after it. A handle with a flight
-// recorder attached takes its host steps through HIP launches: the capture is a launch on the stream, behind the step's.
+// recorder or a spawn bank attached takes its host steps through HIP launches: their kernels are launches on the stream, behind the step's.
 static int host_step(ac_env* h, int set) {
   if (aql_settle(h)) return -1;
   StepPlan sp;
   if (step_plan(h, nullptr, set, &sp)) return -1;
   AqlState& a = h->aql;
-  bool aql = a.mode == AqlState::READY && !h->timing && !h->rec && sp.n == a.nkern;
+  bool aql = a.mode == AqlState::READY && !h->timing && !h->rec && !h->spawn && sp.n == a.nkern;
   for (int i = 0; aql && i < sp.n; ++i) aql = sp.k[i].fn == a.kern[i].fn;
   if (aql) {
     if (stream_settle(h)) return -1;
@@ -1915,6 +1919,7 @@ static int host_step(ac_env* h, int set) {
     return e.empty() ? 0 : aql_fault(h, e);
   }
   if (launch_plan(h, sp)) return -1;
+  if (h->spawn && spawn_hook(h, 0, set)) return -1;
   if (h->rec && recorder_hook(h, 0)) return -1;
   if (a.mode == AqlState::PENDING && !h->timing) {   // the launch above has loaded HIP's code object: its kernel symbols can be resolved
     const std::string e = aql_setup(&a, h->device, sp);
@@ -1940,6 +1945,31 @@ static int launch_reset(ac_env* h) {
 }
 
 #include "flight_recorder.hpp"
+
+// The reset template of initial conditions `ia`, written by the init kernel of the handle's task and shape to (tF, tI, tD): the
+// handle's own template (ac_create) and every entry of a spawn bank (spawn_bank.hpp).
+static void launch_init_template(ac_env* h, const InitArgs& ia, float* tF, int* tI, double* tD) {
+  const ac_config_t* cfg = &h->cfg;
+  const bool scenario = h->d_XF != nullptr;
+  if (cfg->task == AC_TASK_HEADING) {
+    // no reset template: every reset runs the initial-condition procedure on fresh draws inside the kernel
+  } else if (scenario && h->A == 2)
+    hipLaunchKernelGGL(init_kernel_scenario<2>, dim3(1), dim3(64), 0, h->stream, ia, h->dc, h->d_tab, tF, tI, tD);
+  else if (scenario && h->A == 4)
+    hipLaunchKernelGGL(init_kernel_scenario<4>, dim3(1), dim3(64), 0, h->stream, ia, h->dc, h->d_tab, tF, tI, tD);
+  else if (scenario)
+    hipLaunchKernelGGL(init_kernel_scenario<8>, dim3(1), dim3(64), 0, h->stream, ia, h->dc, h->d_tab, tF, tI, tD);
+  else if (cfg->task == AC_TASK_MULTICOMBAT && h->A == 4)
+    hipLaunchKernelGGL(init_kernel_nvn<4>, dim3(1), dim3(64), 0, h->stream, ia, h->dc, h->d_tab, tF, tI, tD);
+  else if (cfg->task == AC_TASK_MULTICOMBAT)
+    hipLaunchKernelGGL(init_kernel_nvn<8>, dim3(1), dim3(64), 0, h->stream, ia, h->dc, h->d_tab, tF, tI, tD);
+  else if (cfg->task == AC_TASK_SINGLECOMBAT)
+    hipLaunchKernelGGL(init_kernel_1v1<AC_TASK_SINGLECOMBAT>, dim3(1), dim3(64), 0, h->stream, ia, h->dc, h->d_tab, tF, tI, tD);
+  else
+    hipLaunchKernelGGL(init_kernel_1v1<AC_TASK_SHOOT_MISSILE>, dim3(1), dim3(64), 0, h->stream, ia, h->dc, h->d_tab, tF, tI, tD);
+}
+
+#include "spawn_bank.hpp"
 
 extern "C" {
 
@@ -2173,22 +2203,7 @@ int ac_create(const ac_config_t* cfg, int32_t n_envs, int32_t device_id, uint64_
   p.tF = h->d_tF; p.tI = h->d_tI; p.tD = h->d_tD; p.tab = h->d_tab; p.actions = h->d_actions;
   InitArgs ia;
   for (int i = 0; i < AC_MAX_AGENTS; ++i) ia.ic[i] = cfg->init[i];
-  if (heading) {
-    // no reset template: every reset runs the initial-condition procedure on fresh draws inside the kernel
-  } else if (scenario && h->A == 2)
-    hipLaunchKernelGGL(init_kernel_scenario<2>, dim3(1), dim3(64), 0, h->stream, ia, h->dc, h->d_tab, h->d_tF, h->d_tI, h->d_tD);
-  else if (scenario && h->A == 4)
-    hipLaunchKernelGGL(init_kernel_scenario<4>, dim3(1), dim3(64), 0, h->stream, ia, h->dc, h->d_tab, h->d_tF, h->d_tI, h->d_tD);
-  else if (scenario)
-    hipLaunchKernelGGL(init_kernel_scenario<8>, dim3(1), dim3(64), 0, h->stream, ia, h->dc, h->d_tab, h->d_tF, h->d_tI, h->d_tD);
-  else if (cfg->task == AC_TASK_MULTICOMBAT && h->A == 4)
-    hipLaunchKernelGGL(init_kernel_nvn<4>, dim3(1), dim3(64), 0, h->stream, ia, h->dc, h->d_tab, h->d_tF, h->d_tI, h->d_tD);
-  else if (cfg->task == AC_TASK_MULTICOMBAT)
-    hipLaunchKernelGGL(init_kernel_nvn<8>, dim3(1), dim3(64), 0, h->stream, ia, h->dc, h->d_tab, h->d_tF, h->d_tI, h->d_tD);
-  else if (cfg->task == AC_TASK_SINGLECOMBAT)
-    hipLaunchKernelGGL(init_kernel_1v1<AC_TASK_SINGLECOMBAT>, dim3(1), dim3(64), 0, h->stream, ia, h->dc, h->d_tab, h->d_tF, h->d_tI, h->d_tD);
-  else
-    hipLaunchKernelGGL(init_kernel_1v1<AC_TASK_SHOOT_MISSILE>, dim3(1), dim3(64), 0, h->stream, ia, h->dc, h->d_tab, h->d_tF, h->d_tI, h->d_tD);
+  launch_init_template(h, ia, h->d_tF, h->d_tI, h->d_tD);
   HIP_OK(hipGetLastError());
   if (launch_reset(h)) return -1;
   HIP_OK(hipStreamSynchronize(h->stream));
@@ -2203,6 +2218,7 @@ int ac_destroy(ac_env_t* h) {
   aql_release(&h->aql);          // the AQL queue, its signal and the kernarg blocks
   (void)hipStreamSynchronize(h->stream);
   recorder_env_gone(h);
+  spawn_env_gone(h);
   void* bufs[] = {h->dp.F, h->dp.D, h->dp.MF, h->dp.MD, h->dp.MI, h->dp.obs, h->dp.rew, h->dp.done, h->dp.info,
                   h->d_actions, h->d_tab, h->d_tF, h->d_tD, h->d_state_io, h->d_XF, h->d_XI, h->dp.H, h->dp.man_step, h->dp.man_h0, h->d_ctlWs8, h->d_low, h->hp.HD, h->hp.HF, h->hp.HI, h->hp.HR,
                   h->d_idx, h->d_clone_tab, h->d_snap_hdr};
@@ -2230,6 +2246,7 @@ int ac_reset(ac_env_t* h, float* obs) {
   HIP_OK(hipStreamSynchronize(h->stream));    // (a step still in flight may yet write the error word)
   *h->err_host = 0; h->err_sticky = 0;
   if (launch_reset(h)) return -1;
+  if (h->spawn && spawn_hook(h, 1, -1)) return -1;
   if (h->rec && recorder_hook(h, 1)) return -1;
   if (obs) HIP_OK(hipMemcpyAsync(obs, h->dp.obs, sizeof(float) * (size_t)h->N * h->obs_dim, hipMemcpyDeviceToHost, h->stream));
   HIP_OK(hipStreamSynchronize(h->stream));
@@ -2356,6 +2373,7 @@ void* ac_stream(ac_env_t* h) {   // (the caller may enqueue on it: a host step s
 }
 const char* ac_dispatch_path(ac_env_t* h) {
   if (!h) return "";
+  if (h->spawn) return "hip: a spawn bank is attached";   // (host_step: its kernel is a launch on the stream behind the step's)
   switch (h->aql.mode) {
     case AqlState::READY: return "aql";
     case AqlState::PENDING: return "pending";     // (the first host step goes through HIP and sets the queue up)

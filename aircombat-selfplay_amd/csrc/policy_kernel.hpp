@@ -21,6 +21,7 @@
 // The MAPPO form (policy_wide_kernel; struct Wide below): the same network with inputs up to 640 wide for both networks and a critic
 // on cent_obs (explicit rows, or each env's observation block); policy_values_kernel is the PPO form's critic-only launch.
 #pragma once
+#include "keyed_uniform.hpp"
 
 namespace pol {
 using ctl::HID;
@@ -88,17 +89,7 @@ struct WideLay {
   __host__ __device__ static constexpr int END(int kpad) { return F0G(kpad) + 2 * kpad; }
 };
 
-// the keyed counter-based generator: a pure function of (seed, counter, row, head), uniform on [0, 1) in steps of 2^-24
-__host__ __device__ __forceinline__ unsigned long long policy_mix(unsigned long long z) {
-  z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ULL; z ^= z >> 27; z *= 0x94D049BB133111EBULL; z ^= z >> 31;
-  return z;
-}
-__host__ __device__ __forceinline__ float policy_uniform(unsigned long long seed, unsigned long long counter, long long row, int head) {
-  unsigned long long z = policy_mix(seed * 0x9E3779B97F4A7C15ULL + 0x6A09E667F3BCC909ULL);
-  z = policy_mix(z ^ (counter * 0xD1B54A32D192ED03ULL));
-  z = policy_mix(z ^ (((unsigned long long)row << 8) | (unsigned long long)(head & 0xff)));
-  return (float)(z >> 40) * (1.0f / 16777216.0f);
-}
+// (the keyed counter-based generator policy_uniform: keyed_uniform.hpp)
 // Where each tensor of one network sits in its fp32 source blob (float offsets; -1 = absent), from the blob order of policy.py
 struct PackMap {
   int obs_dim;

@@ -449,6 +449,33 @@ class HipVecEnv:
         """the attached ``FlightRecorder``, or None"""
         return getattr(self, "_recorder", None)
 
+    def spawn_curriculum(self, angles=None, init_states=None, mode="fixed", sample="at", win_return=None, window=20, win_rate=0.9, seed=0):
+        """Build a bank of reset templates and attach it as a ``SpawnCurriculum`` (spawn.py): ``angles=range(181)`` is the reference's
+        curriculum table for this handle's config, ``init_states=rows`` any ``[K][A]`` spawns (``AcInitState`` rows or dicts with the
+        YAML's ``ic_*`` keys). From now on every env that is reset -- inside a step on whatever path, ``DeviceRollout.collect``,
+        ``DeviceMAPPORollout.collect`` and ``DeviceEvaluator.run`` included, or by ``reset()`` -- respawns from the bank entry its stage
+        selects. ``mode="auto"`` (with ``win_return``) advances stages on the device by the win rate over ``window`` episodes;
+        ``sample="upto"`` draws among the entries up to the stage. One bank is attached at a time; while one is, host steps are
+        dispatched as HIP launches instead of AQL packets."""
+        from .spawn import SpawnCurriculum
+        self._assert_not_closed()
+        return SpawnCurriculum(self, angles=angles, init_states=init_states, mode=mode, sample=sample, win_return=win_return, window=window,
+                               win_rate=win_rate, seed=seed)
+
+    def stop_curriculum(self):
+        """Detach and free the attached bank (nothing attached: nothing happens). Envs keep flying their running episodes; from their
+        next reset on they respawn from the handle's own template again."""
+        self._assert_not_closed()
+        cur = getattr(self, "_curriculum", None)
+        if cur is not None:
+            cur.close()
+        self.lib.check(self.lib.ac_spawn_detach(self._h), "ac_spawn_detach")
+
+    @property
+    def curriculum(self):
+        """the attached ``SpawnCurriculum``, or None"""
+        return getattr(self, "_curriculum", None)
+
     def _ix(self, name):
         if not hasattr(self, "_names"):
             self._names = self.lib.state_field_names()
@@ -465,6 +492,9 @@ class HipVecEnv:
             if rec is not None:
                 rec.close()
         self._recorder = None
+        cur = getattr(self, "_curriculum", None)
+        if cur is not None:                                     # (ac_destroy frees the bank: its views must not outlive it)
+            cur.close()
         if self.copy:
             for st in self._sets:
                 if self._held(st):

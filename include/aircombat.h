@@ -154,8 +154,9 @@ void* ac_stream(ac_env_t* h);   /* hipStream_t the kernels are launched on (crea
 /* How the handle's host steps (ac_step_host_async / ac_step_host) are dispatched: "aql" (one AQL packet on a queue the handle owns, kernargs
  * written once per host set; the default after the first host step), "pending" (before the first host step, which goes through HIP and
  * sets the queue up), "AIRCOMBAT_DISPATCH=hip" (the environment variable, read by ac_create, pins the HIP runtime's launch), or
- * "fallback: <reason>" (the set-up failed or the queue faulted; host steps go through HIP). Host steps inside an ac_timing_begin ..
- * ac_timing_end bracket always go through HIP. The handle owns the returned string. */
+ * "fallback: <reason>" (the set-up failed or the queue faulted; host steps go through HIP), or, while a spawn bank is attached
+ * (aircombat_spawn.h), "hip: a spawn bank is attached". Host steps inside an ac_timing_begin .. ac_timing_end bracket always go
+ * through HIP. The handle owns the returned string. */
 const char* ac_dispatch_path(ac_env_t* h);
 int ac_sync(ac_env_t* h);
 /* Ordering against the caller's streams without a host sync: ac_order_after makes the steps launched from now on wait for the work
