@@ -14,6 +14,7 @@ from .snapshot import EnvSnapshot, MultiSnapshot, SnapshotMismatch  # noqa: F401
 from .policy import DevicePolicy, DeviceMAPPOPolicy, DevicePolicyPool, UnsupportedPolicy  # noqa: F401
 from .rollout import DeviceRollout, DeviceMAPPORollout  # noqa: F401
 from .evaluate import DeviceEvaluator, EvalResult, elo_update  # noqa: F401
+from .league import DeviceLeague, LeagueTable, round_robin  # noqa: F401
 from .recorder import FlightRecorder  # noqa: F401
 from .spawn import SpawnCurriculum  # noqa: F401
 from . import sharding  # noqa: F401
@@ -34,7 +35,7 @@ def __getattr__(name):
 __all__ = ["AcConfig", "AcInitState", "Lib", "load_library", "library_path", "HipExtensionMissing",
            "config_from_yaml", "default_config", "default_nvn_config", "TASK_IDS", "HipVecEnv", "HipShareVecEnv", "MultiDeviceVecEnv", "make_env", "controller_forward",
            "DeviceReplayBuffer", "DeviceSharedReplayBuffer", "EnvSnapshot", "MultiSnapshot", "SnapshotMismatch",
-           "DevicePolicy", "DeviceMAPPOPolicy", "DevicePolicyPool", "UnsupportedPolicy", "DeviceRollout", "DeviceMAPPORollout", "DeviceEvaluator", "EvalResult", "elo_update", "FlightRecorder", "SpawnCurriculum", "curriculum_bank", "DeviceGRUFunction", "DeviceGRULayer", "use_device_gru",
+           "DevicePolicy", "DeviceMAPPOPolicy", "DevicePolicyPool", "UnsupportedPolicy", "DeviceRollout", "DeviceMAPPORollout", "DeviceEvaluator", "EvalResult", "elo_update", "DeviceLeague", "LeagueTable", "round_robin", "FlightRecorder", "SpawnCurriculum", "curriculum_bank", "DeviceGRUFunction", "DeviceGRULayer", "use_device_gru",
            "DeviceMLPBlockFunction", "DeviceMLPLayer", "mlp_block", "use_device_mlp",
            "DeviceActEvalFunction", "act_evaluate", "use_device_act",
            "DevicePPOLossFunction", "ppo_loss", "device_clip_adam_step", "DevicePPOTrainer"]

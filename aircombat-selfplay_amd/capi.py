@@ -84,6 +84,37 @@ class AcEvalPostStep(C.Structure):
                                           "log_len", "log_end", "remaining")]
 
 
+class AcLeagueConfig(C.Structure):
+    """ac_league_config_t (include/aircombat_league.h)"""
+    _fields_ = [("episodes_per_env", C.c_int32), ("deterministic", C.c_int32), ("win_margin", C.c_float), ("pad_", C.c_int32)]
+
+
+class AcLeagueState(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("E", "A", "K", "C", "step", "pad_")] + \
+               [(n, C.c_void_p) for n in ("h", "masks", "cum", "len", "count", "log_ret", "log_len", "log_end", "log_code", "members2",
+                                          "remaining")]
+
+
+class AcLeaguePostStep(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("E", "A", "hidden", "K", "step", "pad_")] + \
+               [(n, C.c_void_p) for n in ("rewards", "dones", "info", "h", "masks", "cum", "len", "count", "log_ret", "log_len", "log_end",
+                                          "log_code", "remaining")]
+
+
+class AcLeagueCell(C.Structure):
+    """ac_league_cell_t: one cell of the payoff table, 64 bytes"""
+    _fields_ = [(n, C.c_int64) for n in ("episodes", "wins_a", "wins_b", "draws", "timeouts", "steps")] + [("sum_a", C.c_double), ("sum_b", C.c_double)]
+
+
+class AcLeagueTableArgs(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("E", "A", "K", "C")] + [("margin", C.c_float), ("pad_", C.c_int32)] + \
+               [(n, C.c_void_p) for n in ("log_ret", "log_len", "log_code", "count", "members2", "out")]
+
+
+AC_LEAGUE_MAX_EPISODES = 64
+AC_DONE_TIMEOUT = 7
+
+
 class AcInitState(C.Structure):
     _fields_ = [(n, C.c_double) for n in
                 ("lon_deg", "lat_geod_deg", "h_sl_ft", "psi_deg", "u_fps", "v_fps", "w_fps",
@@ -251,6 +282,7 @@ SIGNATURES = {
     "ac_policy_pool_copy_from": (C.c_int, [_p, _p, C.c_int32, _p]),
     "ac_policy_pool_packed": (C.c_int, [_p, C.c_int32, C.POINTER(_p), C.POINTER(C.c_int64)]),
     "ac_policy_pool_assign": (C.c_int, [_p, _p, _p, C.c_int64, C.c_int32]),
+    "ac_policy_pool_assign_sides": (C.c_int, [_p, _p, _p, C.c_int64, C.c_int32]),
     "ac_policy_pool_check": (C.c_int, [_p, _p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "ac_policy_pool_plan_host": (C.c_int, [_p, C.c_int64, C.c_int32, C.c_int32, _p, _p, _p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "ac_policy_pool_max_tiles": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
@@ -307,6 +339,15 @@ SIGNATURES = {
     "ac_eval_run": (C.c_int, [_p, _p, C.c_int32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64]),
     "ac_eval_state": (C.c_int, [_p, _p]),
     "ac_eval_post_step_host": (C.c_int, [_p]),
+    # include/aircombat_league.h
+    "ac_league_create": (C.c_int, [_p, _p, _p, C.POINTER(_p)]),
+    "ac_league_destroy": (C.c_int, [_p]),
+    "ac_league_begin": (C.c_int, [_p, _p]),
+    "ac_league_run": (C.c_int, [_p, _p, C.c_int32, C.c_uint64, C.c_uint64]),
+    "ac_league_state": (C.c_int, [_p, _p]),
+    "ac_league_post_step_host": (C.c_int, [_p]),
+    "ac_league_table": (C.c_int, [_p, _p, _p]),
+    "ac_league_table_host": (C.c_int, [_p]),
     # include/aircombat_record.h
     "ac_recorder_layout": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(AcRecorderLayout)]),
     "ac_recorder_create": (C.c_int, [_p, _p, C.c_int32, C.c_int32, C.POINTER(_p)]),

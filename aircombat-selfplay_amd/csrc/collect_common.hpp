@@ -1,5 +1,5 @@
-// What the device collectors share (rollout_collect.hpp: the PPO and the MAPPO rollout; eval_collect.hpp: the evaluator). Included at
-// the end of aircombat.hip ahead of both (same library, same error channel). Two halves:
+// What the device collectors share (rollout_collect.hpp: the PPO and the MAPPO rollout; eval_collect.hpp: the evaluator;
+// league_collect.hpp: the league). Included at the end of aircombat.hip ahead of them (same library, same error channel). Two halves:
 //
 // The row pieces of the post-step kernels, `__host__ __device__` so that the *_post_step_host exports run the very same code. The kernels
 // are streaming kernels with no reuse: ROW_LANES = 32 threads per row, rows = the learner's E * na rows followed by the opponent's
@@ -101,7 +101,7 @@ inline std::string post_step_error(const P& p) {
 struct CollectCore {
   int device;
   ac_env* env;
-  ac_policy_s* learner;
+  ac_policy_s* learner;              // NULL for the league, whose learner step is the pool's whole-range launch
   ac_policy_s* opp_policy;           // opponent_kind 1
   ac_policy_pool_s* opp_pool;        // opponent_kind 2
   int na, kind;                      // AC_ROLLOUT_* opponent kinds; AC_EVAL_*'s are the same three numbers
@@ -178,7 +178,7 @@ inline void core_free(CollectCore* c) {
   for (float* q : {c->d_opp_h, c->d_opp_masks, c->d_opp_logp}) if (q) (void)hipFree(q);
 }
 
-// The loop of ac_rollout_collect, ac_share_rollout_collect and ac_eval_run, as `fn`. Refused before anything is queued or written:
+// The loop of ac_rollout_collect, ac_share_rollout_collect, ac_eval_run and ac_league_run, as `fn`. Refused before anything is queued or written:
 // weights not loaded (the critic's only where the learner's launch uses it), a pool that no longer fits, what the step itself would
 // refuse. Then every launch goes to the env's stream: on entry it is made to wait for the work already queued on `caller` and on
 // `extra` (the buffer's stream, a created one; NULL: there is none), with one event of ev_in each; on return both are made to wait
@@ -189,7 +189,8 @@ int queue_steps(const CollectCore& c, const std::string& fn, hipStream_t caller,
                 hipEvent_t ev_out, int n_steps, uint64_t opponent_seed, uint64_t opponent_counter0, bool needs_critic,
                 LearnerStep learner_step, PostStep post_step) {
   ac_env* env = c.env;
-  if (!c.learner->loaded[0] || (needs_critic && !c.learner->loaded[1])) return fail(fn + ": the learner's weights are not loaded");
+  // (the league has no learner policy: its learner step is the pool's launch, whose members' load state its begin has checked)
+  if (c.learner && (!c.learner->loaded[0] || (needs_critic && !c.learner->loaded[1]))) return fail(fn + ": the learner's weights are not loaded");
   if (c.opp_policy && !c.opp_policy->loaded[0]) return fail(fn + ": the opponent's weights are not loaded");
   if (c.opp_pool && c.opp_pool->E != env->E) return fail(fn + ": the opponent pool's assignment no longer covers the env's E");
   if (c.opp_pool && c.opp_pool->net.wide != c.learner->wide)

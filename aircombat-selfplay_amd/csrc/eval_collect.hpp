@@ -20,28 +20,37 @@ __host__ __device__ inline void eval_one_fewer(int32_t* remaining) {
   --*remaining;
 #endif
 }
+// env e's accounting for one step, P = ac_eval_post_step_t or ac_league_post_step_t (league_collect.hpp): every word of it is read and
+// written by this one item. Returns the log slot the step filled, -1 where it filled none.
+template <class P>
+__host__ __device__ inline int account_env(const P& p, int e) {
+  const int A = p.A, K = p.K;
+  const bool done = env_done(p.dones, A, e);
+  float c[AC_MAX_AGENTS];
+  for (int a = 0; a < A; ++a) c[a] = p.cum[(size_t)e * A + a] + p.rewards[(size_t)e * A + a];
+  const int len = p.len[e] + 1;
+  int logged = -1;
+  if (done) {
+    const int n = p.count[e];
+    if (n < K) {
+      const size_t slot = (size_t)e * K + n;
+      for (int a = 0; a < A; ++a) p.log_ret[slot * A + a] = c[a];
+      p.log_len[slot] = len;
+      p.log_end[slot] = p.step;
+      if (n == K - 1) eval_one_fewer(p.remaining);
+      logged = n;
+    }
+    p.count[e] = n + 1;
+  }
+  for (int a = 0; a < A; ++a) p.cum[(size_t)e * A + a] = done ? 0.0f : c[a];
+  p.len[e] = done ? 0 : len;
+  return logged;
+}
 // work item `item` below eval_post_items, each passed once
 __host__ __device__ inline void eval_post_one(const ac_eval_post_step_t& p, long long item) {
   const long long rows = post_row_items(p);
   if (item >= rows) {   // the env's accounting
-    const int e = (int)(item - rows), A = p.A, K = p.K;
-    const bool done = env_done(p.dones, A, e);
-    float c[AC_MAX_AGENTS];
-    for (int a = 0; a < A; ++a) c[a] = p.cum[(size_t)e * A + a] + p.rewards[(size_t)e * A + a];
-    const int len = p.len[e] + 1;
-    if (done) {
-      const int n = p.count[e];
-      if (n < K) {
-        const size_t slot = (size_t)e * K + n;
-        for (int a = 0; a < A; ++a) p.log_ret[slot * A + a] = c[a];
-        p.log_len[slot] = len;
-        p.log_end[slot] = p.step;
-        if (n == K - 1) eval_one_fewer(p.remaining);
-      }
-      p.count[e] = n + 1;
-    }
-    for (int a = 0; a < A; ++a) p.cum[(size_t)e * A + a] = done ? 0.0f : c[a];
-    p.len[e] = done ? 0 : len;
+    (void)account_env(p, (int)(item - rows));
     return;
   }
   const int lane = (int)(item % ROW_LANES);

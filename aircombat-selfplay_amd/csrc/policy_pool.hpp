@@ -7,6 +7,10 @@
 // with the same refusals. The plan (ac_policy_pool_assign) is a stable counting sort of the call's rows by member, then a list of tiles
 // of at most 32 rows of one member each: pool_plan_phase, one __host__ __device__ function run by one workgroup on the device and by
 // ac_policy_pool_plan_host on the host.
+//
+// A sided assignment (ac_policy_pool_assign_sides, the league's) is the same plan over the 2 E half-envs of A / 2 rows each: half-env
+// 2 e + side, row k, is call row e * A + side * A / 2 + k of the whole-range call, so order[] holds call rows as before and neither the
+// plan kernel nor the act kernels change; only the bookkeeping around them does (pool_units / pool_unit_rows).
 #pragma once
 
 namespace pol {
@@ -125,6 +129,10 @@ struct ac_policy_pool_s {
   int* d_order = nullptr;
   int64_t E = -1, cap_E = 0, cap_rows = 0, cap_tiles = 0;
   int na = 0;
+  // a sided plan (ac_policy_pool_assign_sides): d_members is [E][2] and the plan runs over the 2 E half-envs of na / 2 rows, half-env
+  // 2 e + side, row k being call row e * na + side * na / 2 + k of the whole-range call; E and na stay the env's
+  int sided = 0;
+  uint64_t plan_gen = 0;                  // bumped by every assign: a holder of a snapshot (the league) tells a later re-assignment
   int ntiles_host = -1;                   // the tile count read back by ac_policy_pool_check (-1: not read for this plan)
 };
 
@@ -167,9 +175,14 @@ pol::Plan pool_plan_args(const int* members, int64_t E, int na, int cap, const i
 }
 int64_t pool_scratch_ints(int cap) { return (int64_t)cap * pol::PLAN_T + 1 + pol::PLAN_T + 1 + pol::PLAN_T + cap + 1 + 2; }
 int64_t pool_max_tiles(int64_t E, int na, int cap) { return (E * na + 31) / 32 + std::min<int64_t>(cap, E); }
+// the units of the plan and the rows of each: the envs of na rows, or the half-envs of na / 2 rows of a sided plan
+int64_t pool_units(const ac_policy_pool_s* p) { return p->sided ? 2 * p->E : p->E; }
+int pool_unit_rows(const ac_policy_pool_s* p, int na) { return p->sided ? na / 2 : na; }
 // (re)build the plan for E envs of na rows on `stream` from the assignment in p->d_members
 int pool_build_plan(ac_policy_pool_s* p, hipStream_t s, int na) {
-  const int64_t rows = p->E * na, mt = pool_max_tiles(p->E, na, p->capacity);
+  const int64_t units = pool_units(p);
+  const int ur = pool_unit_rows(p, na);
+  const int64_t rows = p->E * na, mt = pool_max_tiles(units, ur, p->capacity);
   if (rows > p->cap_rows) {
     if (p->d_order) HIP_OK(hipFree(p->d_order));
     p->d_order = nullptr; p->cap_rows = 0;
@@ -182,12 +195,25 @@ int pool_build_plan(ac_policy_pool_s* p, hipStream_t s, int na) {
     HIP_OK(hipMalloc(&p->d_tiles, sizeof(int4) * std::max<int64_t>(mt, 1)));
     p->cap_tiles = mt;
   }
-  const pol::Plan a = pool_plan_args(p->d_members, p->E, na, p->capacity, p->d_loaded, p->d_scratch, p->d_tiles, p->d_order);
+  const pol::Plan a = pool_plan_args(p->d_members, units, ur, p->capacity, p->d_loaded, p->d_scratch, p->d_tiles, p->d_order);
   hipLaunchKernelGGL(policy_pool_plan_kernel, dim3(1), dim3(pol::PLAN_T), 0, s, a);
   HIP_OK(hipGetLastError());
   p->na = na;
   p->ntiles_host = -1;
+  p->plan_gen += 1;
   return 0;
+}
+// the copy of an assignment of `n` ints, its plan on `s`: the tail of both assigns
+int pool_assign(ac_policy_pool_s* p, hipStream_t s, const int32_t* d_members, int64_t n, int64_t E, int na, int sided) {
+  if (n > p->cap_E) {
+    if (p->d_members) HIP_OK(hipFree(p->d_members));
+    p->d_members = nullptr; p->cap_E = 0; p->E = -1;
+    HIP_OK(hipMalloc(&p->d_members, sizeof(int) * n));
+    p->cap_E = n;
+  }
+  HIP_OK(hipMemcpyAsync(p->d_members, d_members, sizeof(int) * n, hipMemcpyDeviceToDevice, s));
+  p->E = E; p->sided = sided;
+  return pool_build_plan(p, s, na);
 }
 }  // namespace
 
@@ -324,16 +350,15 @@ int ac_policy_pool_assign(ac_policy_pool_t* p, void* stream, const int32_t* d_me
   if (!p || !d_members) return fail("ac_policy_pool_assign: null argument");
   if (E < 1 || na < 1 || E * na > (1 << 24)) return fail("ac_policy_pool_assign: E and na must be >= 1 with E * na <= 2^24");
   HIP_OK(hipSetDevice(p->device));
-  hipStream_t s = (hipStream_t)stream;
-  if (E > p->cap_E) {
-    if (p->d_members) HIP_OK(hipFree(p->d_members));
-    p->d_members = nullptr; p->cap_E = 0; p->E = -1;
-    HIP_OK(hipMalloc(&p->d_members, sizeof(int) * E));
-    p->cap_E = E;
-  }
-  HIP_OK(hipMemcpyAsync(p->d_members, d_members, sizeof(int) * E, hipMemcpyDeviceToDevice, s));
-  p->E = E;
-  return pool_build_plan(p, s, na);
+  return pool_assign(p, (hipStream_t)stream, d_members, E, E, na, 0);
+}
+// the sided assignment: members2 [E][2], one member per side of every env, planned over the half-envs for the whole-range call of A rows
+int ac_policy_pool_assign_sides(ac_policy_pool_t* p, void* stream, const int32_t* d_members2, int64_t E, int32_t A) {
+  if (!p || !d_members2) return fail("ac_policy_pool_assign_sides: null argument");
+  if (A < 2 || A % 2) return fail("ac_policy_pool_assign_sides: A must be even and >= 2 (got " + std::to_string(A) + ")");
+  if (E < 1 || E * A > (1 << 24)) return fail("ac_policy_pool_assign_sides: E must be >= 1 with E * A <= 2^24");
+  HIP_OK(hipSetDevice(p->device));
+  return pool_assign(p, (hipStream_t)stream, d_members2, 2 * E, E, A, 1);
 }
 // waits for `stream`: the first env of the plan's assignment whose member is out of range or not loaded (-1: none), and its tile count
 int ac_policy_pool_check(ac_policy_pool_t* p, void* stream, int32_t* bad_env, int32_t* ntiles) {
@@ -344,7 +369,7 @@ int ac_policy_pool_check(ac_policy_pool_t* p, void* stream, int32_t* bad_env, in
   int v[2] = {0, 0};   // ntiles, bad_env (adjacent in the scratch)
   HIP_OK(hipMemcpyAsync(v, a.ntiles, sizeof(v), hipMemcpyDeviceToHost, (hipStream_t)stream));
   HIP_OK(hipStreamSynchronize((hipStream_t)stream));
-  *ntiles = v[0]; *bad_env = v[1];
+  *ntiles = v[0]; *bad_env = p->sided && v[1] >= 0 ? v[1] / 2 : v[1];   // (a sided plan's units are half-envs)
   p->ntiles_host = v[0];
   return 0;
 }
@@ -379,6 +404,11 @@ int ac_policy_pool_act(ac_policy_pool_t* p, void* stream, const ac_policy_rows_t
   if (na == 0) { na = 1; A = 1; }
   if (na < 1 || A < na || rows->a0 < 0 || rows->a0 + na > A || rows->n % na) return fail("ac_policy_pool_act: bad agent range");
   if (rows->act_stride < nh) return fail("ac_policy_pool_act: act_stride is smaller than the number of heads");
+  if (p->sided && (na != p->na || A != p->na || rows->a0 != 0 || rows->n != p->E * p->na))
+    return fail("ac_policy_pool_act: a sided plan (ac_policy_pool_assign_sides) for " + std::to_string(p->E) + " envs of " +
+                std::to_string(p->na) + " agents is in force and takes the whole-range call only (n " + std::to_string(p->E * p->na) +
+                ", na = A = " + std::to_string(p->na) + ", a0 0); the call has n " + std::to_string(rows->n) + ", na " + std::to_string(na) +
+                ", A " + std::to_string(A) + ", a0 " + std::to_string(rows->a0));
   if (rows->n != p->E * na)
     return fail("ac_policy_pool_act: the call has " + std::to_string(rows->n) + " rows, the assignment " + std::to_string(p->E) + " envs of " +
                 std::to_string(na) + " rows");
@@ -397,7 +427,7 @@ int ac_policy_pool_act(ac_policy_pool_t* p, void* stream, const ac_policy_rows_t
   pol::Pool x{};
   x.W0 = p->d_w; x.stride = p->net.packed_n[0]; x.tiles = p->d_tiles; x.order = p->d_order; x.ntiles = pl.ntiles; x.xcd = p->xcd;
   // the exact tile count once ac_policy_pool_check has read it, else the plan's bound (workgroups past the count exit)
-  int64_t nt = p->ntiles_host >= 0 ? p->ntiles_host : pool_max_tiles(p->E, na, p->capacity);
+  int64_t nt = p->ntiles_host >= 0 ? p->ntiles_host : pool_max_tiles(pool_units(p), pool_unit_rows(p, na), p->capacity);
   if (nt == 0) return 0;
   if (p->xcd) nt = (nt + 7) / 8 * 8;
   const dim3 g((unsigned)nt);

@@ -515,6 +515,7 @@ class DevicePolicyPool:
     packs its actor, with one precision for the whole pool. ``assign`` maps each env to a member (-1: not acted for); ``act_into_env`` /
     ``act`` then act for every assigned row with its member's weights, with ``DevicePolicy``'s sampling: draws keyed by (seed, counter,
     row of the call, head), so each row's output is the one a DevicePolicy holding that member would give in the same call.
+    ``assign_sides`` maps each *side* of each env to a member instead, for the one whole-range launch of a league (league.py).
 
     The host-side choice of opponents (``selfplay_algo.choose``, the ELO update) stays the reference's: the runner maps its policy-pool
     keys to member indices, loads them, and calls ``assign``. Assign after loading: a member's load state is
@@ -539,6 +540,7 @@ class DevicePolicyPool:
         self.counter = 0
         self._na = 1        # rows per env of the plan (the agent count of the calls)
         self._members = None
+        self._sided = None   # (E, A) while a sided plan (assign_sides) is in force
         h = C.c_void_p()
         self.lib.check(self.lib.ac_policy_pool_create(self.device_id, C.byref(self.cfg), self._form, self.capacity, C.byref(h)),
                        "ac_policy_pool_create")
@@ -626,6 +628,7 @@ class DevicePolicyPool:
         stream = torch.cuda.current_stream(dev).cuda_stream
         self.lib.check(self.lib.ac_policy_pool_assign(self._h, stream, m.data_ptr(), m.numel(), self._na), "ac_policy_pool_assign")
         self._members = m   # alive until the copy has run
+        self._sided = None
         self.num_envs = int(m.numel())
         if check:
             bad, nt = C.c_int32(), C.c_int32()
@@ -637,6 +640,42 @@ class DevicePolicyPool:
                 raise ValueError(f"assign: env {bad.value} has member {v}, {why}")
         return self
 
+    def assign_sides(self, members2, A, check=True):
+        """The sided assignment of a league (league.py): env e's agents ``[0, A/2)`` act with member ``members2[e][0]``, agents
+        ``[A/2, A)`` with ``members2[e][1]`` (-1: that side is not acted for); ``members2``: numpy or a torch int tensor of shape
+        [E, 2], ``A`` even. Planned on torch's stream like ``assign``. While it is in force only the whole-range call is taken,
+        ``act_into_env(env, h, masks, agents=slice(0, A))`` with [E * A, 1, 128] states: one launch for both sides of every env, each
+        row with its side's member and its own keyed draws. Other ``agents`` and ``act`` raise ``ValueError``; ``assign`` returns the
+        pool to the per-env form. With ``check``, a ValueError names the first env with a member out of range or not loaded."""
+        import torch
+        dev = torch.device("cuda", self.device_id)
+        A = int(A)
+        if A < 2 or A % 2:
+            raise ValueError(f"assign_sides: A must be even and >= 2 (got {A})")
+        if isinstance(members2, torch.Tensor):
+            if members2.dim() != 2 or members2.shape[1] != 2 or members2.is_floating_point():
+                raise ValueError("assign_sides: members2 must be an int tensor of shape [E, 2]")
+            m = members2.to(device=dev, dtype=torch.int32).contiguous()
+        else:
+            m = np.asarray(members2)
+            if m.ndim != 2 or m.shape[1] != 2 or not np.issubdtype(m.dtype, np.integer):
+                raise ValueError("assign_sides: members2 must be an int array of shape [E, 2]")
+            m = torch.as_tensor(np.ascontiguousarray(m, dtype=np.int32)).to(dev)
+        E = int(m.shape[0])
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        self.lib.check(self.lib.ac_policy_pool_assign_sides(self._h, stream, m.data_ptr(), E, A), "ac_policy_pool_assign_sides")
+        self._members = m   # alive until the copy has run
+        self._sided, self._na = (E, A), A
+        self.num_envs = E
+        if check:
+            bad, nt = C.c_int32(), C.c_int32()
+            self.lib.check(self.lib.ac_policy_pool_check(self._h, stream, C.byref(bad), C.byref(nt)), "ac_policy_pool_check")
+            self.num_tiles = int(nt.value)
+            if bad.value >= 0:
+                pair = [int(v) for v in m[bad.value].tolist()]
+                raise ValueError(f"assign_sides: env {bad.value} has members {pair}: out of range (capacity {self.capacity}) or not loaded")
+        return self
+
     def assign_split(self, E, member_ids, check=True, na=None):
         """The reference's split: ``np.array_split(np.arange(E), K)``, range k to ``member_ids[k]``."""
         members = np.empty(int(E), dtype=np.int32)
@@ -646,6 +685,9 @@ class DevicePolicyPool:
 
     # ---- calls
     def _launch(self, rows, obs, h, masks, deterministic, actions, logp, h_out, counter):
+        if self._sided is not None and (rows.na, rows.A, rows.a0, rows.n) != (self._sided[1], self._sided[1], 0, self._sided[0] * self._sided[1]):
+            raise ValueError(f"a sided plan (assign_sides) for {self._sided[0]} envs of {self._sided[1]} agents is in force: only "
+                             "act_into_env(..., agents=slice(0, A)) over every agent of every env is taken (assign() returns to the per-env form)")
         if counter is None:
             counter = self.counter
             self.counter += 1

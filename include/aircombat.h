@@ -364,6 +364,14 @@ int ac_policy_pool_packed(ac_policy_pool_t* p, int32_t member, void** d_ptr, int
  * Copied and planned on `stream` (a stable sort of the rows by member, tiles of <= 32 rows of one member); the plan is kept for every
  * later ac_policy_pool_act, and rebuilt by a call whose na differs. */
 int ac_policy_pool_assign(ac_policy_pool_t* p, void* stream, const int32_t* d_members, int64_t E, int32_t na);
+/* the sided assignment (the league, aircombat_league.h): members2 is [E][2]: env e's agents [0, A/2) act with members2[e][0], agents
+ * [A/2, A) with members2[e][1] (-1: that side is not acted for). A even, >= 2. Planned on `stream` like ac_policy_pool_assign, as that
+ * plan over the 2 E half-envs of A / 2 rows: half-env 2 e + side, row k is call row e * A + side * A / 2 + k. While it is in force
+ * ac_policy_pool_act takes exactly the whole-range call (rows->n = E * A, rows->na = rows->A = A, rows->a0 = 0), one launch in which row
+ * e * A + a acts with its side's member and the row's own keyed draws; any other geometry is refused, naming the sided plan, and the
+ * plan is never rebuilt by a call. ac_policy_pool_check reports the first bad env (not half-env); ac_policy_pool_max_tiles and
+ * ac_policy_pool_plan_host describe the plan with (2 E, A / 2). A later ac_policy_pool_assign returns the pool to the per-env form. */
+int ac_policy_pool_assign_sides(ac_policy_pool_t* p, void* stream, const int32_t* d_members2, int64_t E, int32_t A);
 /* waits for `stream`: the first env whose member is out of range or not loaded (-1: none; such envs are not acted for) and the plan's
  * tile count, which later act calls then use as their grid */
 int ac_policy_pool_check(ac_policy_pool_t* p, void* stream, int32_t* bad_env, int32_t* ntiles);
