@@ -20,6 +20,8 @@ from .spawn import SpawnCurriculum  # noqa: F401
 from . import sharding  # noqa: F401
 
 _TORCH_EXPORTS = {"DeviceGRUFunction": "gru_train", "DeviceGRULayer": "gru_train", "use_device_gru": "gru_train",
+                  "DeviceGRULayerFunction": "gru_layer_train", "gru_layer": "gru_layer_train", "DeviceFusedGRULayer": "gru_layer_train",
+                  "use_device_gru_layer": "gru_layer_train",
                   "DeviceMLPBlockFunction": "mlp_train", "DeviceMLPLayer": "mlp_train", "mlp_block": "mlp_train", "use_device_mlp": "mlp_train",
                   "DeviceActEvalFunction": "act_train", "act_evaluate": "act_train", "use_device_act": "act_train",
                   "DevicePPOLossFunction": "ppo_update", "ppo_loss": "ppo_update", "device_clip_adam_step": "ppo_update", "DevicePPOTrainer": "ppo_update"}
@@ -36,6 +38,7 @@ __all__ = ["AcConfig", "AcInitState", "Lib", "load_library", "library_path", "Hi
            "config_from_yaml", "default_config", "default_nvn_config", "TASK_IDS", "HipVecEnv", "HipShareVecEnv", "MultiDeviceVecEnv", "make_env", "controller_forward",
            "DeviceReplayBuffer", "DeviceSharedReplayBuffer", "EnvSnapshot", "MultiSnapshot", "SnapshotMismatch",
            "DevicePolicy", "DeviceMAPPOPolicy", "DevicePolicyPool", "UnsupportedPolicy", "DeviceRollout", "DeviceMAPPORollout", "DeviceEvaluator", "EvalResult", "elo_update", "DeviceLeague", "LeagueTable", "round_robin", "FlightRecorder", "SpawnCurriculum", "curriculum_bank", "DeviceGRUFunction", "DeviceGRULayer", "use_device_gru",
+           "DeviceGRULayerFunction", "gru_layer", "DeviceFusedGRULayer", "use_device_gru_layer",
            "DeviceMLPBlockFunction", "DeviceMLPLayer", "mlp_block", "use_device_mlp",
            "DeviceActEvalFunction", "act_evaluate", "use_device_act",
            "DevicePPOLossFunction", "ppo_loss", "device_clip_adam_step", "DevicePPOTrainer"]

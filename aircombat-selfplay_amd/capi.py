@@ -290,6 +290,10 @@ SIGNATURES = {
     "ac_policy_pool_act": (C.c_int, [_p, _p, _p, _p, _p, _p, C.c_int32, C.c_uint64, C.c_uint64, _p, _p, _p]),
     "ac_gru_seq_forward": (C.c_int, [C.c_int32, _p, C.c_int32, C.c_int32, _p, _p, _p, _p, _p, _p, _p, _p]),
     "ac_gru_seq_backward": (C.c_int, [C.c_int32, _p, C.c_int32, C.c_int32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "ac_gru_layer_workspace_floats": (C.c_int64, [C.c_int32, C.c_int32]),
+    "ac_gru_layer_forward": (C.c_int, [C.c_int32, _p, C.c_int32, C.c_int32] + [_p] * 9 + [C.c_float] + [_p] * 6),
+    "ac_gru_layer_backward": (C.c_int, [C.c_int32, _p, C.c_int32, C.c_int32] + [_p] * 20),
+    "ac_gru_layer_constant": (C.c_int32, [C.c_int32]),
     "ac_mlp_block_workspace_floats": (C.c_int64, [C.c_int32, C.c_int32]),
     "ac_mlp_block_forward": (C.c_int, [C.c_int32, _p, C.c_int32, C.c_int32, C.c_float, _p, _p, _p, _p, _p, _p, _p]),
     "ac_mlp_block_backward": (C.c_int, [C.c_int32, _p, C.c_int32, C.c_int32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),

@@ -1,7 +1,7 @@
 // The PPO update's GRU on the device ("The training GRU"): the reference's one-layer GRULayer (algorithms/utils/gru.py),
 // input 128, hidden 128, torch's gate order r, z, n and n = tanh(Wi_n x + b_in + r * (Wh_n h + b_hn)), over a whole minibatch of
 // chunks in one launch per direction. Rows are T-major ([T * N, .], row t * N + j = step t of chunk j), as recurrent_generator yields
-// them. The input products Gi = x W_ihᵀ + b_ih and the weight gradients are single large GEMMs the caller runs in torch; what is here is
+// them. The input products Gi = x W_ihᵀ + b_ih and the weight gradients are large GEMMs the caller runs (torch, or the kernels of gru_layer_train.hpp); what is here is
 // the recurrence torch cannot batch: the hidden product, the gates, the masks and the reverse-time loop.
 //
 // One workgroup of eight waves owns 16 chunks (one 16-row M-tile) for all T steps. Wave w owns hidden units 16 w .. 16 w + 15, and W_hh

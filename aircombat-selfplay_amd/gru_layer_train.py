@@ -1,0 +1,168 @@
+"""The PPO / MAPPO update's whole recurrent layer on the device ("The whole GRU layer").
+
+``DeviceFusedGRULayer`` is ``DeviceGRULayer`` (gru_train.py) with nothing left to torch: the input product ``x W_ihᵀ + b_ih``, the
+recurrence, the LayerNorm and, backward, the LayerNorm's gradients, ``dx``, ``dW_ih``, ``dW_hh`` and the bias sums are HIP kernels
+(csrc/gru_layer_train.hpp around the recurrence kernels of csrc/gru_train.hpp), queued by one C call per direction on torch's current
+stream. It has the same children (``gru``, ``norm``), so the same Parameter objects and state_dict keys.
+
+``use_device_gru_layer(policy)`` swaps every GRULayer-shaped child of a policy, and every ``DeviceGRULayer`` that ``use_device_gru``
+put there, for a ``DeviceFusedGRULayer`` holding the same two submodules. Nothing selects it unless the caller asks.
+"""
+import torch
+import torch.nn as nn
+
+from . import capi
+from . import gru_train
+from .gru_train import HID, SAVED, DeviceGRULayer
+from .policy import UnsupportedPolicy
+
+
+def _call(what, rc, lib):
+    if rc != 0:
+        raise RuntimeError(f"{what} failed: {lib.last_error()}")
+
+
+class DeviceGRULayerFunction(torch.autograd.Function):
+    """(x [T*N, 128], hxs [N, 128], masks [T*N], W_ih, W_hh, b_ih, b_hh, gamma, beta, eps, save) -> (out [T*N, 128] after the
+    LayerNorm, h_T [N, 128]).
+
+    Each step starts from ``h_{t-1} * m_t``. With ``save`` the forward keeps the recurrence's outputs and gates and each row's mean
+    and 1/std; ``apply`` is called through ``gru_layer``, which decides that (inside ``forward`` grad mode is always off and
+    ``needs_input_grad`` ignores it). The backward computes ``dx`` and ``dhxs`` only when asked, and returns a parameter's gradient
+    only where ``needs_input_grad`` asks."""
+
+    @staticmethod
+    def forward(ctx, x, hxs, masks, w_ih, w_hh, b_ih, b_hh, gamma, beta, eps, save):
+        lib = capi.load_library()
+        N = hxs.shape[0]
+        T = x.shape[0] // N
+        dev = x.device
+        x, hxs, masks, w_ih, w_hh, b_ih, b_hh, gamma, beta = (t.contiguous() for t in (x, hxs, masks, w_ih, w_hh, b_ih, b_hh, gamma, beta))
+        new = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)
+        # the gate pre-activations live in a torch tensor: torch's allocator orders its reuse on this stream
+        ws = new(T * N * 3 * HID)
+        out, h_T, y = new(T * N, HID), new(N, HID), new(T * N, HID)
+        saved, stats = (new(T * N, SAVED), new(T * N, 2)) if save else (None, None)
+        ptr = lambda t: None if t is None else t.data_ptr()
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _call("ac_gru_layer_forward", lib.ac_gru_layer_forward(dev.index, stream, N, T, x.data_ptr(), hxs.data_ptr(), masks.data_ptr(),
+                                                               w_ih.data_ptr(), w_hh.data_ptr(), b_ih.data_ptr(), b_hh.data_ptr(),
+                                                               gamma.data_ptr(), beta.data_ptr(), eps, ws.data_ptr(), out.data_ptr(),
+                                                               h_T.data_ptr(), y.data_ptr(), ptr(saved), ptr(stats)), lib)
+        if save:
+            ctx.save_for_backward(x, hxs, masks, w_ih, w_hh, gamma, y, saved, stats)
+            ctx.shape = (N, T)
+        ctx.set_materialize_grads(False)
+        return out, h_T
+
+    @staticmethod
+    def backward(ctx, g_out, g_h):
+        lib = capi.load_library()
+        x, hxs, masks, w_ih, w_hh, gamma, y, saved, stats = ctx.saved_tensors
+        N, T = ctx.shape
+        dev = x.device
+        need = ctx.needs_input_grad
+        new = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)
+        ws = new(lib.ac_gru_layer_workspace_floats(N, T))
+        dx = new(T * N, HID) if need[0] else None
+        dhxs = new(N, HID) if need[1] else None
+        dw_ih, dw_hh, db_ih, db_hh, dgamma, dbeta = new(3 * HID, HID), new(3 * HID, HID), new(3 * HID), new(3 * HID), new(HID), new(HID)
+        g_out = None if g_out is None else g_out.contiguous()
+        g_h = None if g_h is None else g_h.contiguous()
+        ptr = lambda t: None if t is None else t.data_ptr()
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _call("ac_gru_layer_backward", lib.ac_gru_layer_backward(dev.index, stream, N, T, ptr(g_out), ptr(g_h), x.data_ptr(), hxs.data_ptr(),
+                                                                 masks.data_ptr(), w_ih.data_ptr(), w_hh.data_ptr(), gamma.data_ptr(),
+                                                                 y.data_ptr(), saved.data_ptr(), stats.data_ptr(), ws.data_ptr(), ptr(dx),
+                                                                 ptr(dhxs), dw_ih.data_ptr(), dw_hh.data_ptr(), db_ih.data_ptr(),
+                                                                 db_hh.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr()), lib)
+        grads = (dx, dhxs, None, dw_ih, dw_hh, db_ih, db_hh, dgamma, dbeta, None, None)
+        return tuple(g if n else None for g, n in zip(grads, need))
+
+
+def gru_layer(x, hxs, masks, w_ih, w_hh, b_ih, b_hh, gamma, beta, eps=1e-5):
+    """The whole layer as a function: DeviceGRULayerFunction with its ``save`` decided here (grad mode on and some input requiring
+    grad). x [T*N, 128], hxs [N, 128], masks [T*N], float32 on one CUDA device -> (out [T*N, 128], h_T [N, 128])."""
+    for name, t in (("x", x), ("hxs", hxs), ("masks", masks)):   # no torch op inside would notice: the kernels read float32 as given
+        if t.dtype != torch.float32 or t.device != w_ih.device:
+            raise UnsupportedPolicy(f"gru_layer: {name} is {t.dtype} on {t.device} (only float32 on {w_ih.device})")
+    if x.dim() != 2 or x.shape[1] != HID or tuple(hxs.shape[1:]) != (HID,) or hxs.shape[0] < 1 or x.shape[0] % hxs.shape[0] or masks.numel() != x.shape[0]:
+        raise ValueError(f"gru_layer: x {tuple(x.shape)}, hxs {tuple(hxs.shape)}, masks {tuple(masks.shape)} are not [T*N, {HID}], [N, {HID}], [T*N]")
+    save = torch.is_grad_enabled() and any(t.requires_grad for t in (x, hxs, w_ih, w_hh, b_ih, b_hh, gamma, beta))
+    return DeviceGRULayerFunction.apply(x, hxs, masks, w_ih, w_hh, b_ih, b_hh, gamma, beta, float(eps), save)
+
+
+def check_layer(gru, norm, where="rnn"):
+    """UnsupportedPolicy unless (gru, norm) is what the kernels run: whatever check_gru accepts, then nn.LayerNorm((128,)) with affine
+    parameters, float32 on a CUDA device."""
+    said = []   # everything wrong with the layer in one message: the GRU's part as check_gru words it, then the LayerNorm's
+    try:
+        gru_train.check_gru(gru, where + ".gru")
+    except UnsupportedPolicy as exc:
+        said.append(str(exc))
+    bad = []
+    if not isinstance(norm, nn.LayerNorm):
+        bad.append(f"not an nn.LayerNorm ({type(norm).__name__})")
+    else:
+        if tuple(norm.normalized_shape) != (HID,):
+            bad.append(f"LayerNorm over {tuple(norm.normalized_shape)} (only ({HID},))")
+        if norm.weight is None or norm.bias is None:
+            bad.append("LayerNorm without affine parameters")
+        for name, p in norm.named_parameters():
+            if p.dtype != torch.float32:
+                bad.append(f"{name} dtype {p.dtype} (only float32)")
+            if p.device.type != "cuda":
+                bad.append(f"{name} device {p.device} (only a CUDA device)")
+    if bad:
+        said.append(f"{where}.norm: " + ", ".join(bad))
+    if said:
+        raise UnsupportedPolicy("; ".join(said))
+
+
+class DeviceFusedGRULayer(DeviceGRULayer):
+    """DeviceGRULayer with the whole layer on the device: the same children ``gru`` and ``norm``, the same forward(x, hxs, masks) ->
+    (out, h_T [N, 1, 128]) and the same T = 1 rule when ``x.size(0) == hxs.size(0)``, as one autograd function with no torch op
+    inside."""
+
+    def forward(self, x, hxs, masks):
+        g, ln = self.gru, self.norm
+        check_layer(g, ln, type(self).__name__)
+        N = hxs.size(0)
+        T = 1 if x.size(0) == N else x.size(0) // N
+        if T * N != x.size(0):
+            raise ValueError(f"x has {x.size(0)} rows, not a multiple of hxs' {N}")
+        out, h_T = gru_layer(x, hxs.reshape(N, HID), masks.reshape(T * N).to(torch.float32), g.weight_ih_l0, g.weight_hh_l0, g.bias_ih_l0,
+                             g.bias_hh_l0, ln.weight, ln.bias, ln.eps)
+        return out, h_T.view(N, 1, HID)
+
+
+def _swappable(m):
+    if isinstance(m, DeviceFusedGRULayer):
+        return False
+    return isinstance(m, DeviceGRULayer) or gru_train._gru_layer_shaped(m)
+
+
+def use_device_gru_layer(module):
+    """Swap every GRULayer-shaped child of ``module`` (a module with an nn.GRU ``gru`` and an nn.LayerNorm ``norm``), and every
+    DeviceGRULayer that use_device_gru put there, for a DeviceFusedGRULayer holding the same two submodules. ``module`` is an nn.Module
+    (``policy.actor``, ``policy.critic``) or an object with ``actor`` / ``critic`` modules. Every layer is checked before any is
+    swapped; an unsupported one raises UnsupportedPolicy naming it. Returns the number of layers swapped."""
+    roots = [(module, "")] if isinstance(module, nn.Module) else \
+        [(getattr(module, k), k + ".") for k in ("actor", "critic") if isinstance(getattr(module, k, None), nn.Module)]
+    if not roots:
+        raise UnsupportedPolicy(f"{type(module).__name__}: neither an nn.Module nor an object with actor / critic modules")
+    found = []
+    for root, prefix in roots:
+        if _swappable(root):
+            raise UnsupportedPolicy(f"{prefix or type(root).__name__}: a GRULayer itself cannot be swapped in place; pass the module holding it")
+        for pname, parent in root.named_modules():
+            for cname, child in parent.named_children():
+                if _swappable(child):
+                    found.append((parent, cname, child, prefix + (pname + "." if pname else "") + cname))
+    for _, _, child, where in found:
+        check_layer(child.gru, child.norm, where)
+        if getattr(child, "_num_layers", 1) != 1:
+            raise UnsupportedPolicy(f"{where}: {child._num_layers} layers (only 1)")
+    for parent, cname, child, _ in found:
+        setattr(parent, cname, DeviceFusedGRULayer(child.gru.input_size, child.gru.hidden_size, child.gru.num_layers, gru=child.gru, norm=child.norm))
+    return len(found)

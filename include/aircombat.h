@@ -404,6 +404,33 @@ int ac_gru_seq_backward(int32_t device_id, void* stream, int32_t N, int32_t T, c
                         const float* d_y, const float* d_hxs, const float* d_masks, const float* d_w_hh, float* d_dgi, float* d_dgh,
                         float* d_dhxs);
 
+/* ---- the whole GRU layer of the PPO update on the device ("The whole GRU layer"): the reference's GRULayer, nn.GRU
+ * 128 -> 128 of one layer then nn.LayerNorm(128), as one call per direction: the input product, the recurrence above, the LayerNorm and,
+ * backward, the weight, bias and input gradients. Shapes, row order and masks as above; every pointer is a device pointer of float32;
+ * the calls launch on `stream` and return at once. Refused before any launch: a NULL required pointer, N or T < 1, N * T beyond the
+ * kernels' 32-bit row index, and a [., 128] array, the workspace or the stats that is not 16-byte aligned. */
+/* floats of d_workspace for this shape (the gate pre-activations or their gradients, and one set of parameter-gradient partial sums
+ * per workgroup); the forward uses the first T * N * 384 of them only; -1: refused */
+int64_t ac_gru_layer_workspace_floats(int32_t N, int32_t T);
+/* forward, three launches: d_x [T*N, 128], d_hxs [N, 128], d_masks [T*N], d_w_ih, d_w_hh [384, 128], d_b_ih, d_b_hh [384], d_gamma,
+ * d_beta [128] and the LayerNorm's eps -> d_out [T*N, 128], d_h_T [N, 128], and d_y [T*N, 128] (the recurrence's outputs before the
+ * LayerNorm). For a backward also d_saved [T*N, 512] and d_stats [T*N, 2] (each row's mean and 1 / sqrt(var + eps)); both NULL: the
+ * inference form, nothing kept. */
+int ac_gru_layer_forward(int32_t device_id, void* stream, int32_t N, int32_t T, const float* d_x, const float* d_hxs, const float* d_masks,
+                         const float* d_w_ih, const float* d_w_hh, const float* d_b_ih, const float* d_b_hh, const float* d_gamma,
+                         const float* d_beta, float eps, float* d_workspace, float* d_out, float* d_h_T, float* d_y, float* d_saved,
+                         float* d_stats);
+/* backward: upstream d_g_out [T*N, 128] (of d_out) and d_g_h_T [N, 128] (either NULL = zero), the forward's inputs and its d_y, d_saved,
+ * d_stats -> d_dx [T*N, 128] (NULL: not computed), d_dhxs [N, 128] (NULL: not computed), d_dw_ih, d_dw_hh [384, 128], d_db_ih, d_db_hh
+ * [384], d_dgamma, d_dbeta [128]. Results are bit-identical from run to run (no atomics). */
+int ac_gru_layer_backward(int32_t device_id, void* stream, int32_t N, int32_t T, const float* d_g_out, const float* d_g_h_T, const float* d_x,
+                          const float* d_hxs, const float* d_masks, const float* d_w_ih, const float* d_w_hh, const float* d_gamma,
+                          const float* d_y, const float* d_saved, const float* d_stats, float* d_workspace, float* d_dx, float* d_dhxs,
+                          float* d_dw_ih, float* d_dw_hh, float* d_db_ih, float* d_db_hh, float* d_dgamma, float* d_dbeta);
+/* the kernels' constants, for tests that size themselves: 0 rows per tile (every kernel), then the workgroups at most of 1 the input
+ * product, 2 the LayerNorm forward, 3 the LayerNorm backward, 4 the weight gradients (per gradient), 5 the input gradient; -1 otherwise */
+int32_t ac_gru_layer_constant(int32_t which);
+
 /* ---- the PPO update's MLP layers on the device ("The training MLP blocks"): one block of the reference's MLPLayer,
  * y = LayerNorm_128(relu(x Wᵀ + b)) * gamma + beta, x [M, K], W [128, K] (nn.Linear's layout), b, gamma, beta [128], biased variance.
  * Every pointer is a device pointer of float32; the calls launch on `stream` and return at once. Refused: a NULL required pointer,
