@@ -9,7 +9,7 @@ or through the repo-root alias module ``aircombat_selfplay_amd``.
 from .capi import AcConfig, AcInitState, Lib, load_library, library_path, HipExtensionMissing  # noqa: F401
 from .config import config_from_yaml, default_config, default_nvn_config, curriculum_bank, TASK_IDS  # noqa: F401
 from .vec_env import HipVecEnv, HipShareVecEnv, MultiDeviceVecEnv, make_env, controller_forward  # noqa: F401
-from .rollout_buffer import DeviceReplayBuffer, DeviceSharedReplayBuffer  # noqa: F401
+from .rollout_buffer import DeviceReplayBuffer, DeviceSharedReplayBuffer, DeviceEpoch  # noqa: F401
 from .snapshot import EnvSnapshot, MultiSnapshot, SnapshotMismatch  # noqa: F401
 from .policy import DevicePolicy, DeviceMAPPOPolicy, DevicePolicyPool, UnsupportedPolicy  # noqa: F401
 from .rollout import DeviceRollout, DeviceMAPPORollout  # noqa: F401
@@ -36,7 +36,7 @@ def __getattr__(name):
 
 __all__ = ["AcConfig", "AcInitState", "Lib", "load_library", "library_path", "HipExtensionMissing",
            "config_from_yaml", "default_config", "default_nvn_config", "TASK_IDS", "HipVecEnv", "HipShareVecEnv", "MultiDeviceVecEnv", "make_env", "controller_forward",
-           "DeviceReplayBuffer", "DeviceSharedReplayBuffer", "EnvSnapshot", "MultiSnapshot", "SnapshotMismatch",
+           "DeviceReplayBuffer", "DeviceSharedReplayBuffer", "DeviceEpoch", "EnvSnapshot", "MultiSnapshot", "SnapshotMismatch",
            "DevicePolicy", "DeviceMAPPOPolicy", "DevicePolicyPool", "UnsupportedPolicy", "DeviceRollout", "DeviceMAPPORollout", "DeviceEvaluator", "EvalResult", "elo_update", "DeviceLeague", "LeagueTable", "round_robin", "FlightRecorder", "SpawnCurriculum", "curriculum_bank", "DeviceGRUFunction", "DeviceGRULayer", "use_device_gru",
            "DeviceGRULayerFunction", "gru_layer", "DeviceFusedGRULayer", "use_device_gru_layer",
            "DeviceMLPBlockFunction", "DeviceMLPLayer", "mlp_block", "use_device_mlp",

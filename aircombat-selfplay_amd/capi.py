@@ -25,6 +25,10 @@ class HipExtensionMissing(RuntimeError):
 # ---- include/aircombat_buffer.h
 (AC_BUF_OBS, AC_BUF_SHARE_OBS, AC_BUF_ACTIONS, AC_BUF_REWARDS, AC_BUF_MASKS, AC_BUF_BAD_MASKS, AC_BUF_ACTIVE_MASKS, AC_BUF_LOGP,
  AC_BUF_VALUES, AC_BUF_RETURNS, AC_BUF_RNN_ACTOR, AC_BUF_RNN_CRITIC, AC_BUF_ADVANTAGES, AC_BUF_NFIELDS) = range(14)
+# ---- include/aircombat_epoch.h: the fields of a mini-batch, named as AcBufferBatch's members and in their order
+AC_EPOCH_FIELDS = ("obs", "share_obs", "actions", "masks", "active_masks", "action_log_probs", "advantages", "returns", "value_preds",
+                   "rnn_states_actor", "rnn_states_critic")
+AC_EPOCH_NFIELDS = len(AC_EPOCH_FIELDS)
 
 
 class AcBufferConfig(C.Structure):
@@ -324,6 +328,13 @@ SIGNATURES = {
     "ac_buffer_read": (C.c_int, [_p, C.c_int32, _p]),
     "ac_buffer_write_slot": (C.c_int, [_p, C.c_int32, C.c_int32, _p]),
     "ac_buffer_last_kernel_ms": (C.c_int, [_p, C.POINTER(C.c_float)]),
+    # include/aircombat_epoch.h
+    "ac_buffer_compute_returns_on": (C.c_int, [_p, _p, _p]),
+    "ac_buffer_advantages_on": (C.c_int, [_p, _p]),
+    "ac_buffer_epoch_layout": (C.c_int, [_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "ac_buffer_epoch_layout_for": (C.c_int, [C.POINTER(AcBufferConfig), C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "ac_buffer_gather_epoch": (C.c_int, [_p, _p, _p, C.c_int32, C.c_int32, C.c_int32, _p]),
+    "ac_buffer_epoch_source_row_host": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     # include/aircombat_rollout.h
     "ac_rollout_create": (C.c_int, [_p, _p, _p, _p, _p, C.POINTER(_p)]),
     "ac_rollout_destroy": (C.c_int, [_p]),

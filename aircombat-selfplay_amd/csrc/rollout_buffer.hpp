@@ -24,6 +24,7 @@ struct ac_buffer {
   float* d_stage; int64_t stage_cap;     // device staging for host-side mini-batch outputs
   hipEvent_t ev0, ev1;
   float last_ms;
+  hipEvent_t ev_in, ev_out;     // the stream-ordered calls' entry and exit ordering (epoch_gather.hpp)
 };
 
 namespace rbuf {
@@ -193,6 +194,7 @@ ac_buffer_t* ac_buffer_create(const ac_buffer_config_t* cfg, int device_id) {
   const int dims[AC_BUF_NFIELDS] = {cfg->obs_dim, cfg->share_obs_dim, cfg->act_dim, 1, 1, 1, cfg->share_obs_dim > 0 ? 1 : 0, cfg->logp_dim, 1, 1, hid, hid, 1};
   const int slots[AC_BUF_NFIELDS] = {T + 1, T + 1, T, T, T + 1, T + 1, T + 1, T, T + 1, T + 1, T + 1, T + 1, T};
   bool ok = hipStreamCreate(&b->stream) == hipSuccess && hipEventCreate(&b->ev0) == hipSuccess && hipEventCreate(&b->ev1) == hipSuccess;
+  ok = ok && hipEventCreateWithFlags(&b->ev_in, hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&b->ev_out, hipEventDisableTiming) == hipSuccess;
   for (int k = 0; k < AC_BUF_NFIELDS && ok; ++k) {
     b->dim[k] = dims[k]; b->slots[k] = slots[k];
     if (dims[k] > 0) ok = hipMalloc(&b->f[k], (size_t)buf_count(b, k) * sizeof(float)) == hipSuccess;
@@ -211,19 +213,22 @@ void ac_buffer_destroy(ac_buffer_t* b) {
   if (b->d_stage) (void)hipFree(b->d_stage);
   if (b->ev0) (void)hipEventDestroy(b->ev0);
   if (b->ev1) (void)hipEventDestroy(b->ev1);
+  if (b->ev_in) (void)hipEventDestroy(b->ev_in);
+  if (b->ev_out) (void)hipEventDestroy(b->ev_out);
   if (b->stream) (void)hipStreamDestroy(b->stream);
   delete b;
 }
 
 int ac_buffer_step_index(const ac_buffer_t* b) { return b ? b->step : -1; }
 
-static int buf_put(ac_buffer* b, int fld, int t, const float* src, int on_device) {
+static int buf_put_on(ac_buffer* b, int fld, int t, const float* src, int on_device, hipStream_t stream) {
   if (!src) return 0;
   if (!b->f[fld]) return fail("ac_buffer: this buffer has no such field (share_obs / active_masks need share_obs_dim > 0)");
   const size_t n = (size_t)b->N * b->dim[fld];
-  HIP_OK(hipMemcpyAsync(b->f[fld] + (size_t)t * n, src, n * sizeof(float), on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, b->stream));
+  HIP_OK(hipMemcpyAsync(b->f[fld] + (size_t)t * n, src, n * sizeof(float), on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, stream));
   return 0;
 }
+static int buf_put(ac_buffer* b, int fld, int t, const float* src, int on_device) { return buf_put_on(b, fld, t, src, on_device, b->stream); }
 
 int ac_buffer_insert(ac_buffer_t* b, const ac_buffer_step_t* s, int on_device) {
   if (!b || !s) return fail("ac_buffer_insert: null argument");
@@ -273,27 +278,36 @@ int ac_buffer_clear(ac_buffer_t* b) {
   return buf_reset_arrays(b);
 }
 
-int ac_buffer_compute_returns(ac_buffer_t* b, const float* next_value, int on_device) {
-  if (!b || !next_value) return fail("ac_buffer_compute_returns: null argument");
-  HIP_OK(hipSetDevice(b->device));
+// value_preds[-1] = next_value (GAE) / returns[-1] = next_value (buffer.py:143,151,158,165), on `stream`
+static int buf_put_next_value(ac_buffer* b, const float* next_value, int on_device, hipStream_t stream) {
+  return buf_put_on(b, b->cfg.use_gae ? AC_BUF_VALUES : AC_BUF_RETURNS, b->T, next_value, on_device, stream);
+}
+// the launch of compute_returns on `stream`: one instantiation per (use_gae, use_proper_time_limits), one grid per tiling
+static int buf_launch_returns(ac_buffer* b, hipStream_t stream) {
   const int T = b->T, N = b->N;
   const bool gae = b->cfg.use_gae, proper = b->cfg.use_proper_time_limits;
-  // value_preds[-1] = next_value (GAE) / returns[-1] = next_value (buffer.py:143,151,158,165)
-  if (buf_put(b, gae ? AC_BUF_VALUES : AC_BUF_RETURNS, T, next_value, on_device)) return -1;
   const float g = (float)b->cfg.gamma, gl = (float)(b->cfg.gamma * b->cfg.gae_lambda);
   const float *r = b->f[AC_BUF_REWARDS], *v = b->f[AC_BUF_VALUES], *m = b->f[AC_BUF_MASKS], *bm = b->f[AC_BUF_BAD_MASKS];
   float* R = b->f[AC_BUF_RETURNS];
   const bool wide = N >= 64 * 256;   // enough 64-column workgroups for every CU
   dim3 grid(wide ? (N + 63) / 64 : (N + 31) / 32), block(rbuf::NT_ALL);
-  HIP_OK(hipEventRecord(b->ev0, b->stream));
 #define AC_RET(G, P)                                                                                                                \
   do {                                                                                                                              \
-    if (wide) hipLaunchKernelGGL((rbuf::returns_kernel<G, P, 64, 64>), grid, block, 0, b->stream, r, v, m, bm, R, T, N, g, gl);     \
-    else hipLaunchKernelGGL((rbuf::returns_kernel<G, P, 32, 128>), grid, block, 0, b->stream, r, v, m, bm, R, T, N, g, gl);        \
+    if (wide) hipLaunchKernelGGL((rbuf::returns_kernel<G, P, 64, 64>), grid, block, 0, stream, r, v, m, bm, R, T, N, g, gl);        \
+    else hipLaunchKernelGGL((rbuf::returns_kernel<G, P, 32, 128>), grid, block, 0, stream, r, v, m, bm, R, T, N, g, gl);           \
   } while (0)
   if (gae && proper) AC_RET(true, true); else if (gae) AC_RET(true, false); else if (proper) AC_RET(false, true); else AC_RET(false, false);
 #undef AC_RET
   HIP_OK(hipGetLastError());
+  return 0;
+}
+
+int ac_buffer_compute_returns(ac_buffer_t* b, const float* next_value, int on_device) {
+  if (!b || !next_value) return fail("ac_buffer_compute_returns: null argument");
+  HIP_OK(hipSetDevice(b->device));
+  if (buf_put_next_value(b, next_value, on_device, b->stream)) return -1;
+  HIP_OK(hipEventRecord(b->ev0, b->stream));
+  if (buf_launch_returns(b, b->stream)) return -1;
   HIP_OK(hipEventRecord(b->ev1, b->stream));
   HIP_OK(hipStreamSynchronize(b->stream));
   HIP_OK(hipEventElapsedTime(&b->last_ms, b->ev0, b->ev1));
@@ -306,17 +320,23 @@ int ac_buffer_last_kernel_ms(ac_buffer_t* b, float* ms) {
   return 0;
 }
 
+// the `advantages` property on `stream`: the statistics' reset and the three kernels
+static int buf_launch_advantages(ac_buffer* b, hipStream_t stream) {
+  const int64_t count = (int64_t)b->T * b->N;
+  HIP_OK(hipMemsetAsync(b->d_stat, 0, 2 * sizeof(double), stream));
+  const int blocks = (int)std::min<int64_t>(2048, (count + 255) / 256);
+  float* adv = b->f[AC_BUF_ADVANTAGES];
+  hipLaunchKernelGGL(rbuf::advantage_stats_kernel, dim3(blocks), dim3(256), 0, stream, b->f[AC_BUF_RETURNS], b->f[AC_BUF_VALUES], adv, count, b->d_stat, 0);
+  hipLaunchKernelGGL(rbuf::advantage_stats_kernel, dim3(blocks), dim3(256), 0, stream, b->f[AC_BUF_RETURNS], b->f[AC_BUF_VALUES], adv, count, b->d_stat, 1);
+  hipLaunchKernelGGL(rbuf::advantage_normalise_kernel, dim3(blocks), dim3(256), 0, stream, adv, count, b->d_stat);
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
 int ac_buffer_advantages(ac_buffer_t* b) {
   if (!b) return fail("ac_buffer_advantages: null handle");
   HIP_OK(hipSetDevice(b->device));
-  const int64_t count = (int64_t)b->T * b->N;
-  HIP_OK(hipMemsetAsync(b->d_stat, 0, 2 * sizeof(double), b->stream));
-  const int blocks = (int)std::min<int64_t>(2048, (count + 255) / 256);
-  float* adv = b->f[AC_BUF_ADVANTAGES];
-  hipLaunchKernelGGL(rbuf::advantage_stats_kernel, dim3(blocks), dim3(256), 0, b->stream, b->f[AC_BUF_RETURNS], b->f[AC_BUF_VALUES], adv, count, b->d_stat, 0);
-  hipLaunchKernelGGL(rbuf::advantage_stats_kernel, dim3(blocks), dim3(256), 0, b->stream, b->f[AC_BUF_RETURNS], b->f[AC_BUF_VALUES], adv, count, b->d_stat, 1);
-  hipLaunchKernelGGL(rbuf::advantage_normalise_kernel, dim3(blocks), dim3(256), 0, b->stream, adv, count, b->d_stat);
-  HIP_OK(hipGetLastError());
+  if (buf_launch_advantages(b, b->stream)) return -1;
   HIP_OK(hipStreamSynchronize(b->stream));
   return 0;
 }

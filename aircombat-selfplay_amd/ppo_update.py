@@ -240,6 +240,7 @@ class DevicePPOTrainer:
         self.use_recurrent_policy = args.use_recurrent_policy
         self.data_chunk_length = args.data_chunk_length
         self.use_policy_active_masks = bool(getattr(args, "use_policy_active_masks", False))
+        self.use_stream_ordered_minibatches = bool(getattr(args, "use_stream_ordered_minibatches", False))
 
     def _to(self, x):
         return (torch.from_numpy(x) if isinstance(x, np.ndarray) else x).to(**self.tpdv)
@@ -285,18 +286,34 @@ class DevicePPOTrainer:
             return buffer.recurrent_generator(buffer.advantages, n, L)
         return type(one).recurrent_generator(buffer, n, L)   # the reference's ReplayBuffer, or a list of them (ppo_trainer.py:87)
 
-    def train(self, policy, buffer, chunk_orders=None):
+    def _epoch(self, buffer, chunk_order=None):
+        """One epoch's minibatches of a device buffer from one launch (``buffer.epoch``), no host wait."""
+        from .rollout_buffer import DeviceReplayBuffer
+        one = buffer[0] if isinstance(buffer, (list, tuple)) and len(buffer) == 1 else buffer
+        if not isinstance(one, DeviceReplayBuffer):
+            raise ValueError("train: stream_ordered minibatches need a DeviceReplayBuffer / DeviceSharedReplayBuffer (the reference's buffers gather on the host)")
+        return one.epoch(self.num_mini_batch, self.data_chunk_length, chunk_order=chunk_order)
+
+    def train(self, policy, buffer, chunk_orders=None, stream_ordered=None):
         """The reference's ``train``: ppo_epoch passes over num_mini_batch minibatches, and the same ``train_info`` dict with the same
         averaging. Every minibatch's six scalars go to one row of a device tensor that is read once at the end. ``buffer`` is one of
         the reference's buffers or a DeviceReplayBuffer / DeviceSharedReplayBuffer (asked for ``on_device=True``). ``chunk_orders``
-        (tests): one chunk permutation per epoch for a device buffer instead of torch.randperm."""
+        (tests): one chunk permutation per epoch for a device buffer instead of torch.randperm.
+
+        ``stream_ordered`` (None: ``args.use_stream_ordered_minibatches``, absent: False): each epoch is one ``buffer.epoch(...)`` on
+        torch's current stream instead of the generator, whose every minibatch waits for the device twice; the read at the end is
+        then the only host wait of the whole call. Without ``chunk_orders`` the permutations come from torch's DEVICE generator
+        (``buffer.epoch``). A device buffer only: ValueError otherwise."""
         if not self.use_recurrent_policy:
             raise NotImplementedError
+        if stream_ordered is None:
+            stream_ordered = self.use_stream_ordered_minibatches
         num_updates = self.ppo_epoch * self.num_mini_batch
         rows = torch.zeros(num_updates, 6, **self.tpdv)
         i = 0
         for epoch in range(self.ppo_epoch):
-            for sample in self._generator(buffer, None if chunk_orders is None else chunk_orders[epoch]):
+            order = None if chunk_orders is None else chunk_orders[epoch]
+            for sample in (self._epoch(buffer, order) if stream_ordered else self._generator(buffer, order)):
                 stats, norms = self._update(policy, sample)
                 rows[i, :4].copy_(stats[capi.AC_PPO_STAT_POLICY_LOSS:capi.AC_PPO_STAT_RATIO_MEAN + 1])   # in the order of _ROW
                 rows[i, 4:].copy_(norms)

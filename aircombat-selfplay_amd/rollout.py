@@ -153,15 +153,22 @@ class DeviceRollout:
             raise ValueError(self.lib.last_error())
         return n_steps
 
-    def compute_returns(self):
+    def compute_returns(self, wait=True):
         """The runners' ``compute()``, which ends a rollout and waits for it: ``policy.get_values`` on the buffer's last slot, queued on
         the stream the last ``collect`` was given (which that call ordered after the rollout), then
-        ``buffer.compute_returns(next_values, on_device=True)``, which is a blocking call of the buffer's. Returns ``next_values``."""
+        ``buffer.compute_returns(next_values, on_device=True)``, which is a blocking call of the buffer's. Returns ``next_values``.
+
+        ``wait=False`` queues both on that stream and returns without a ``synchronize``: ``get_values`` and
+        ``buffer.compute_returns(next_values, on_device=True, wait=False)``. The returns (and ``next_values``) are there when the stream
+        gets there; ``buffer.epoch`` or ``DevicePPOTrainer.train(..., stream_ordered=True)`` on the same stream follow without a wait."""
         import torch
         b, T = self.buffer, self.buffer.buffer_size
         stream = getattr(self, "_last_stream", None) or torch.cuda.current_stream(torch.device("cuda", self.device_id))
         with torch.cuda.stream(stream):
             next_values = self.policy.get_values(self._critic_input(T), b.device_tensor("rnn_states_critic")[T], b.device_tensor("masks")[T])
+            if not wait:
+                b.compute_returns(next_values, on_device=True, wait=False)
+                return next_values
         stream.synchronize()   # the buffer copies next_values on its own stream
         b.compute_returns(next_values, on_device=True)
         return next_values

@@ -7,6 +7,10 @@ numpy arrays (the reference's call, runner/jsbsim_runner.py:133) or device point
 (the env handle's own output buffers: no host round trip); ``compute_returns`` runs the reference's float32 recurrence as a HIP
 kernel and is bit-identical to the numpy code; ``recurrent_generator`` gathers each mini-batch on the device.
 
+Those calls block. ``compute_returns(..., wait=False)``, ``queue_advantages()`` and ``epoch(...)`` (a ``DeviceEpoch``: every mini-batch
+of an epoch from one launch) are their stream-ordered forms behind ``include/aircombat_epoch.h``: queued on torch's current stream,
+nothing waited for on the host.
+
 There is no CPU implementation here: without the HIP library the constructor raises ``HipExtensionMissing``.
 """
 import ctypes as C
@@ -14,7 +18,7 @@ import ctypes as C
 import numpy as np
 
 from . import capi
-from .capi import (AcBufferBatch, AcBufferConfig, AcBufferStep, AC_BUF_ACTIONS, AC_BUF_ACTIVE_MASKS, AC_BUF_ADVANTAGES, AC_BUF_BAD_MASKS,
+from .capi import (AcBufferBatch, AcBufferConfig, AcBufferStep, AC_EPOCH_FIELDS, AC_EPOCH_NFIELDS, AC_BUF_ACTIONS, AC_BUF_ACTIVE_MASKS, AC_BUF_ADVANTAGES, AC_BUF_BAD_MASKS,
                    AC_BUF_LOGP, AC_BUF_MASKS, AC_BUF_OBS, AC_BUF_RETURNS, AC_BUF_REWARDS, AC_BUF_RNN_ACTOR, AC_BUF_RNN_CRITIC,
                    AC_BUF_SHARE_OBS, AC_BUF_VALUES)
 
@@ -36,6 +40,27 @@ def shape_from_space(space):
 
 def _host(x):
     return np.ascontiguousarray(np.asarray(x), dtype=np.float32)
+
+
+class DeviceEpoch:
+    """The mini-batches of one epoch (``buffer.epoch(...)``), gathered by one launch into one flat float32 tensor on the buffer's GPU.
+    ``len(epoch)`` mini-batches; ``epoch[i]`` (and iteration) gives the tuple ``minibatch(..., on_device=True)`` returns for
+    ``order[i * mb:(i + 1) * mb]``: 9 entries for the PPO buffer, 11 for the shared one, same names, order, shapes and dtype, as views
+    into ``flat``, which they keep alive. ``order`` is the device int32 tensor of the ``len(epoch) * mb`` chunk indices used. Everything is
+    queued on the stream that was current when the epoch was made: read it on that stream, or after waiting for it."""
+
+    def __init__(self, flat, order, batches, names):
+        self.flat, self.order, self.names = flat, order, names
+        self._batches = batches
+
+    def __len__(self):
+        return len(self._batches)
+
+    def __getitem__(self, i):
+        return self._batches[i]
+
+    def __iter__(self):
+        return iter(self._batches)
 
 
 class DeviceReplayBuffer:
@@ -139,8 +164,20 @@ class DeviceReplayBuffer:
     def clear(self):
         self._ok(self.lib.ac_buffer_clear(self._h), "ac_buffer_clear")
 
-    def compute_returns(self, next_value, on_device=False):
-        if on_device:
+    def _current_stream(self):
+        import torch
+        return torch.cuda.current_stream(torch.device("cuda", self.device_id)).cuda_stream
+
+    def compute_returns(self, next_value, on_device=False, wait=True):
+        """buffer.py:134-167. ``wait=False`` (with ``on_device=True`` only: a host array could be reused before it is read) queues the
+        same copy and the same kernel on torch's current stream and returns at once; ``next_value`` must have been produced on that
+        stream (or be complete), and ``last_returns_kernel_ms`` is not updated."""
+        if not wait:
+            if not on_device:
+                raise ValueError("compute_returns: wait=False takes a device next_value (on_device=True)")
+            p = int(next_value) if isinstance(next_value, (int, np.integer)) else int(next_value.data_ptr())
+            self._ok(self.lib.ac_buffer_compute_returns_on(self._h, self._current_stream(), p), "ac_buffer_compute_returns_on")
+        elif on_device:
             p = int(next_value) if isinstance(next_value, (int, np.integer)) else int(next_value.data_ptr())
             self._ok(self.lib.ac_buffer_compute_returns(self._h, p, 1), "ac_buffer_compute_returns")
         else:
@@ -158,6 +195,11 @@ class DeviceReplayBuffer:
         """buffer.py:72-75 (host copy; the generator below reads the device array)."""
         self._ok(self.lib.ac_buffer_advantages(self._h), "ac_buffer_advantages")
         return self.array("advantages")
+
+    def queue_advantages(self):
+        """The ``advantages`` property's three kernels queued on torch's current stream, nothing waited for and nothing returned: the
+        normalised advantages are in ``device_tensor("advantages")`` when the stream gets there."""
+        self._ok(self.lib.ac_buffer_advantages_on(self._h, self._current_stream()), "ac_buffer_advantages_on")
 
     # names of the per-step arrays of a mini-batch, in the order the reference yields them
     _BATCH = ("obs", "actions", "masks", "action_log_probs", "advantages", "returns", "value_preds")
@@ -187,6 +229,65 @@ class DeviceReplayBuffer:
             batch = AcBufferBatch(**{k: v.ctypes.data for k, v in outs.items()})
         self._ok(self.lib.ac_buffer_minibatch(self._h, chunks.ctypes.data, n, L, C.byref(batch), int(bool(on_device))), "ac_buffer_minibatch")
         return tuple(outs[k] for k in self._BATCH) + (outs["rnn_states_actor"], outs["rnn_states_critic"])
+
+    def epoch(self, num_mini_batch, data_chunk_length, chunk_order=None):
+        """Every mini-batch of one pass of ``recurrent_generator(..., on_device=True)`` as a ``DeviceEpoch``, without a host wait: one
+        flat tensor from torch's allocator (safe without a wait: everything here runs on torch's current stream), the advantages
+        (``queue_advantages``) and ONE gather launch for all fields of all mini-batches. The number of chunks, the mini-batch size and
+        the dropped remainder are ``recurrent_generator``'s: ``data_chunks = n_rollout_threads * buffer_size // data_chunk_length``,
+        ``mb = data_chunks // num_mini_batch``, and the chunks past ``num_mini_batch * mb`` of the order are not used.
+
+        ``chunk_order=None`` draws ``torch.randperm(data_chunks, device=...)`` ON THE DEVICE, i.e. from torch's device generator and
+        not from the CPU generator the reference and ``recurrent_generator`` draw from: under one ``torch.manual_seed`` the two give
+        different (equally uniform) permutations. A host array (numpy, list, CPU tensor) is checked on the host exactly as
+        ``minibatch`` checks its chunks and sent through pinned memory without blocking. An integer tensor on the buffer's GPU is
+        used as it is, unchecked: the kernel clamps every index into the valid range, which keeps a bad index from reading
+        outside the buffer but does not report it."""
+        import torch
+        n_mb, L = int(num_mini_batch), int(data_chunk_length)
+        assert self.n_rollout_threads * self.buffer_size >= L, "PPO requires n_rollout_threads * buffer_size >= data_chunk_length"
+        data_chunks = self.n_rollout_threads * self.buffer_size // L
+        mb = data_chunks // n_mb
+        if n_mb < 1 or mb < 1:
+            raise ValueError(f"epoch: {data_chunks} chunks do not fill {n_mb} mini-batches")
+        dev, used = torch.device("cuda", self.device_id), n_mb * mb
+        with torch.cuda.device(dev):
+            if chunk_order is None:
+                order = torch.randperm(data_chunks, device=dev)[:used].to(torch.int32)
+            elif isinstance(chunk_order, torch.Tensor) and chunk_order.device.type == "cuda":
+                if chunk_order.device != dev or chunk_order.dtype.is_floating_point or chunk_order.dtype == torch.bool or chunk_order.numel() < used:
+                    raise ValueError(f"epoch: chunk_order must be an integer tensor of at least {used} indices on {dev}")
+                order = chunk_order.reshape(-1)[:used].to(torch.int32).contiguous()
+            else:
+                host = np.ascontiguousarray(np.asarray(chunk_order).reshape(-1)[:used], dtype=np.int32)
+                if host.size < used:
+                    raise ValueError(f"epoch: chunk_order holds {host.size} indices, {used} are needed")
+                rows = self.buffer_size * self.n_rollout_threads * self.num_agents
+                if (host < 0).any() or ((host.astype(np.int64) + 1) * L > rows).any():
+                    raise RuntimeError("epoch failed: chunk index outside the buffer")
+                pinned = torch.empty(used, dtype=torch.int32, pin_memory=True)
+                pinned.numpy()[:] = host
+                order = pinned.to(dev, non_blocking=True)   # torch's host allocator orders the reuse of `pinned` after the copy
+            offsets, total = (C.c_int64 * AC_EPOCH_NFIELDS)(), C.c_int64()
+            self._ok(self.lib.ac_buffer_epoch_layout(self._h, n_mb, mb, L, offsets, C.byref(total)), "ac_buffer_epoch_layout")
+            flat = torch.empty(total.value, dtype=torch.float32, device=dev)
+            self.queue_advantages()
+            self._ok(self.lib.ac_buffer_gather_epoch(self._h, self._current_stream(), order.data_ptr(), n_mb, mb, L, flat.data_ptr()),
+                     "ac_buffer_gather_epoch")
+        widths = {"obs": self.obs_shape, "share_obs": self.share_obs_shape, "actions": self.act_shape, "masks": (1,), "active_masks": (1,),
+                  "action_log_probs": self._shapes["action_log_probs"][3:], "advantages": (1,), "returns": (1,), "value_preds": (1,)}
+        hid = (self.recurrent_hidden_layers, self.recurrent_hidden_size)
+        names = self._BATCH + ("rnn_states_actor", "rnn_states_critic")
+        batches = []
+        for i in range(n_mb):
+            item = []
+            for k in names:
+                shape = ((mb,) + hid) if k.startswith("rnn_states") else ((L * mb,) + tuple(widths[k]))
+                n = int(np.prod(shape))
+                at = offsets[AC_EPOCH_FIELDS.index(k)] + i * n
+                item.append(flat[at:at + n].view(shape))
+            batches.append(tuple(item))
+        return DeviceEpoch(flat, order, batches, names)
 
     @staticmethod
     def recurrent_generator(buffer, num_mini_batch, data_chunk_length, chunk_order=None, on_device=False):
