@@ -24,7 +24,8 @@ _TORCH_EXPORTS = {"DeviceGRUFunction": "gru_train", "DeviceGRULayer": "gru_train
                   "use_device_gru_layer": "gru_layer_train",
                   "DeviceMLPBlockFunction": "mlp_train", "DeviceMLPLayer": "mlp_train", "mlp_block": "mlp_train", "use_device_mlp": "mlp_train",
                   "DeviceActEvalFunction": "act_train", "act_evaluate": "act_train", "use_device_act": "act_train",
-                  "DevicePPOLossFunction": "ppo_update", "ppo_loss": "ppo_update", "device_clip_adam_step": "ppo_update", "DevicePPOTrainer": "ppo_update"}
+                  "DevicePPOLossFunction": "ppo_update", "ppo_loss": "ppo_update", "device_clip_adam_step": "ppo_update", "DevicePPOTrainer": "ppo_update",
+                  "DeviceDiscriminator": "mutual_support"}
 
 
 def __getattr__(name):
@@ -41,4 +42,4 @@ __all__ = ["AcConfig", "AcInitState", "Lib", "load_library", "library_path", "Hi
            "DeviceGRULayerFunction", "gru_layer", "DeviceFusedGRULayer", "use_device_gru_layer",
            "DeviceMLPBlockFunction", "DeviceMLPLayer", "mlp_block", "use_device_mlp",
            "DeviceActEvalFunction", "act_evaluate", "use_device_act",
-           "DevicePPOLossFunction", "ppo_loss", "device_clip_adam_step", "DevicePPOTrainer"]
+           "DevicePPOLossFunction", "ppo_loss", "device_clip_adam_step", "DevicePPOTrainer", "DeviceDiscriminator"]

@@ -202,6 +202,24 @@ class AcSpawnPostStep(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("E", "A", "n_ego", "K", "all_envs", "pad_")] + [("cfg", AcSpawnConfig)] + \
                [(n, C.c_void_p) for n in ("rewards", "info", "stage", "spawned", "episode", "ret_acc", "wins", "played", "return_sum", "index")]
 
+
+# ---- include/aircombat_mutual.h
+AC_MI_HIDDEN, AC_MI_WIDTH, AC_MI_MAX_ACT, AC_MI_MAX_OBS = 128, 256, 12, 128
+AC_MI_WEIGHTS = ("p_w0", "p_b0", "p_w1", "p_b1", "p_w2", "p_b2", "q_w0", "q_b0", "q_w1", "q_b1", "q_w2", "q_b2")
+
+
+class AcMiScore(C.Structure):
+    """ac_mi_score_t: the mutual-support scorer's arguments."""
+    _fields_ = [(n, C.c_int32) for n in ("E", "na", "T", "obs_dim", "act_dim", "hidden", "s0", "n", "add")] + [("ratio", C.c_float)] + \
+               [(n, C.c_void_p) for n in ("OBS", "ACTIONS", "RNN_ACTOR", "REWARDS") + AC_MI_WEIGHTS + ("r_int", "mse")]
+
+
+class AcMiGather(C.Structure):
+    """ac_mi_gather_t: the gather of one discriminator mini-batch."""
+    _fields_ = [(n, C.c_int32) for n in ("E", "na", "T", "obs_dim", "act_dim", "hidden", "m", "pad_")] + \
+               [(n, C.c_void_p) for n in ("OBS", "ACTIONS", "RNN_ACTOR", "times", "X", "Y")]
+
+
 AC_PPO_STAT_LOSS, AC_PPO_STAT_POLICY_LOSS, AC_PPO_STAT_VALUE_LOSS, AC_PPO_STAT_ENTROPY_LOSS, AC_PPO_STAT_RATIO_MEAN, AC_PPO_STAT_DENOMINATOR = range(6)
 AC_PPO_NSTAT = 8
 
@@ -383,6 +401,11 @@ SIGNATURES = {
     "ac_spawn_state": (C.c_int, [_p, _p]),
     "ac_spawn_post_step_host": (C.c_int, [_p]),
     "ac_spawn_draw_host": (C.c_int, [C.c_uint64, C.c_int64, C.c_int64, C.c_int32, C.POINTER(C.c_int32)]),
+    # include/aircombat_mutual.h
+    "ac_mi_score": (C.c_int, [_p, _p]),
+    "ac_mi_score_host": (C.c_int, [_p]),
+    "ac_mi_gather": (C.c_int, [_p, _p]),
+    "ac_mi_gather_host": (C.c_int, [_p]),
 }
 
 

@@ -2871,3 +2871,4 @@ int ac_get_missile_target(ac_env_t* h, int32_t env, int32_t agent, int32_t k, in
 #include "eval_collect.hpp"
 #include "league_collect.hpp"
 #include "gru_layer_train.hpp"
+#include "mutual_support.hpp"

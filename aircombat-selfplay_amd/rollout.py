@@ -16,8 +16,9 @@ a ``DeviceSharedReplayBuffer`` and, for self-play, an actor-only ``DeviceMAPPOPo
 post-step kernel (the same file's share form) also writes ``share_obs``, ``active_masks`` and the log-probs once per head column;
 the results are bit for bit those of the stepwise loop of INTEGRATION.md §5e.
 
-Out of scope for both: the per-step ``infos`` history, ``MultiDeviceVecEnv`` (one collector per device) and graph capture; for the
-MAPPO form also the mutual-support ``Discriminator``, whose intrinsic rewards change ``rewards`` before ``insert``.
+Out of scope for both: the per-step ``infos`` history, ``MultiDeviceVecEnv`` (one collector per device) and graph capture. The
+mutual-support ``Discriminator`` of the MAPPO form needs no hook here: its intrinsic rewards are one launch after ``collect()``
+(``DeviceDiscriminator.intrinsic_rewards``).
 """
 import ctypes as C
 
