@@ -17,15 +17,11 @@ import torch.nn as nn
 
 from . import capi
 from .policy import UnsupportedPolicy
+from .train_common import Launch, linear_faults, policy_roots
 
 HID = 128           # in-features of every head
 MAX_CAT = 8         # categorical heads at most
 MAX_LOGITS = 160    # their logits at most
-
-
-def _call(what, rc, lib):
-    if rc != 0:
-        raise RuntimeError(f"{what} failed: {lib.last_error()}")
 
 
 def _ptrs(tensors):
@@ -41,17 +37,13 @@ class DeviceActEvalFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, action, alpha0, beta0, nvec, n_shoot_cols, save, *params):
-        lib = capi.load_library()
         heads = capi.AcActHeads(n_cat=len(nvec), n_shoot_cols=n_shoot_cols)
         heads.nvec[:len(nvec)] = list(nvec)
         params = tuple(p.contiguous() for p in params)
-        M, dev = x.shape[0], x.device
-        logp = torch.empty(M, dtype=torch.float32, device=dev)
-        ent = torch.empty(M, dtype=torch.float32, device=dev)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        _call("ac_act_eval_forward", lib.ac_act_eval_forward(dev.index, stream, C.byref(heads), M, x.data_ptr(), _ptrs(params[0::2]), _ptrs(params[1::2]),
-                                                             action.data_ptr(), None if alpha0 is None else alpha0.data_ptr(),
-                                                             None if beta0 is None else beta0.data_ptr(), logp.data_ptr(), ent.data_ptr()), lib)
+        M = x.shape[0]
+        run = Launch(x)
+        logp, ent = run.empty(M), run.empty(M)
+        run("ac_act_eval_forward", C.byref(heads), M, x, _ptrs(params[0::2]), _ptrs(params[1::2]), action, alpha0, beta0, logp, ent)
         if save:
             ctx.heads, ctx.shoot = heads, alpha0 is not None
             ctx.set_materialize_grads(False)   # an unused output's gradient arrives as None and goes to the kernel as NULL
@@ -60,24 +52,18 @@ class DeviceActEvalFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dlogp, dent):
-        lib = capi.load_library()
         x, action, *rest = ctx.saved_tensors
         alpha0, beta0 = (rest[0], rest[1]) if ctx.shoot else (None, None)
         params = rest[2:] if ctx.shoot else rest
-        M, dev = x.shape[0], x.device
+        M = x.shape[0]
         dlogp = None if dlogp is None else dlogp.contiguous()
         dent = None if dent is None else dent.contiguous()
-        new = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)
-        # the partial sums live in a torch tensor: torch's allocator orders its reuse on this stream
-        ws = new(lib.ac_act_eval_workspace_floats(C.byref(ctx.heads), M))
-        dx = new(M, HID) if ctx.needs_input_grad[0] else None
+        run = Launch(x)
+        ws = run.workspace("ac_act_eval_workspace_floats", C.byref(ctx.heads), M)   # the partial sums
+        dx = run.empty(M, HID) if ctx.needs_input_grad[0] else None
         grads = [torch.empty_like(p) for p in params]
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        _call("ac_act_eval_backward", lib.ac_act_eval_backward(dev.index, stream, C.byref(ctx.heads), M, None if dlogp is None else dlogp.data_ptr(),
-                                                               None if dent is None else dent.data_ptr(), x.data_ptr(), _ptrs(params[0::2]),
-                                                               _ptrs(params[1::2]), action.data_ptr(), None if alpha0 is None else alpha0.data_ptr(),
-                                                               None if beta0 is None else beta0.data_ptr(), ws.data_ptr(),
-                                                               None if dx is None else dx.data_ptr(), _ptrs(grads[0::2]), _ptrs(grads[1::2])), lib)
+        run("ac_act_eval_backward", C.byref(ctx.heads), M, dlogp, dent, x, _ptrs(params[0::2]), _ptrs(params[1::2]), action, alpha0, beta0, ws,
+            dx, _ptrs(grads[0::2]), _ptrs(grads[1::2]))
         return (dx, None, None, None, None, None, None, *grads)
 
 
@@ -122,12 +108,7 @@ def check_heads(action_outs, where="action_outs", device=True):
             bad.append(f"{at}: {lin.out_features} logits (at least 2)")
         if i >= len(cats) and lin.out_features != 2:
             bad.append(f"{at}: out-features {lin.out_features} (only 2)")
-        if lin.bias is None:
-            bad.append(f"{at}: Linear without bias")
-        if lin.weight.dtype != torch.float32:
-            bad.append(f"{at}: dtype {lin.weight.dtype} (only float32)")
-        if device and lin.weight.device.type != "cuda":
-            bad.append(f"{at}: device {lin.weight.device} (only a CUDA device)")
+        bad += [f"{at}: {fault}" for fault in linear_faults(lin, device)]
     nvec = [lin.out_features for lin in linears[:len(cats)] if isinstance(lin, nn.Linear)]
     if sum(nvec) > MAX_LOGITS:
         bad.append(f"{sum(nvec)} logits (at most {MAX_LOGITS})")
@@ -189,12 +170,8 @@ def use_device_act(module):
     Parameter objects and ``forward`` stay as they are; ``copy.deepcopy`` of it runs the device path too. Every layer is checked before
     any is changed; an unsupported one (a single ``action_out``: Discrete, Box, MultiBinary) raises UnsupportedPolicy naming it.
     Returns the number of layers changed."""
-    roots = [(module, "")] if isinstance(module, nn.Module) else \
-        [(getattr(module, k), k + ".") for k in ("actor", "critic") if isinstance(getattr(module, k, None), nn.Module)]
-    if not roots:
-        raise UnsupportedPolicy(f"{type(module).__name__}: neither an nn.Module nor an object with actor / critic modules")
     found = []
-    for root, prefix in roots:
+    for root, prefix in policy_roots(module):
         for name, m in root.named_modules():
             if _act_layer_shaped(m) and not _swapped(m):
                 found.append((m, prefix + name if name else (prefix.rstrip(".") or type(root).__name__)))

@@ -347,18 +347,12 @@ __global__ __launch_bounds__(512) void act_eval_bwd(const float* __restrict__ dl
   }
 }
 
-// dW_h, db_h of every head = the sum of the G partial sets, in an order fixed by G alone: eight interleaved running sums, then a tree
+// dW_h, db_h of every head = the sum of the G partial sets (trn::sum_sets)
 __global__ __launch_bounds__(256) void act_eval_reduce(const float* __restrict__ ws, int G, const Heads hd, const Grads gr) {
   const int nel = (H + 1) * hd.total;
   const int e = blockIdx.x * 256 + threadIdx.x;
   if (e >= nel) return;
-  float a[8] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-  int g = 0;
-  for (; g + 8 <= G; g += 8)
-#pragma unroll
-    for (int j = 0; j < 8; ++j) a[j] += ws[(size_t)(g + j) * nel + e];
-  for (int j = 0; g < G; ++g, ++j) a[j] += ws[(size_t)g * nel + e];
-  const float s = ((a[0] + a[1]) + (a[2] + a[3])) + ((a[4] + a[5]) + (a[6] + a[7]));
+  const float s = trn::sum_sets(ws, G, nel, e);
   const bool isw = e < H * hd.total;
   const int c = isw ? e / H : e - H * hd.total;
   float* dst = nullptr;
@@ -388,7 +382,7 @@ static int act_heads_ok(const char* who, const ac_act_heads_t* hs, int32_t M, in
   }
   if (sum > actt::MAX_LOGITS) return fail(w + ": the heads have " + std::to_string(sum) + " logits (at most 160)");
   if (hs->n_shoot_cols != 0 && hs->n_shoot_cols != 1 && hs->n_shoot_cols != 4) return fail(w + ": n_shoot_cols must be 0, 1 or 4");
-  if ((int64_t)M * mlpt::H > (int64_t)INT32_MAX - mlpt::RT * mlpt::H) return fail(w + ": M * 128 exceeds the kernels' 32-bit index");
+  if (trn::rows_fit_i32(w, M, mlpt::H, mlpt::RT)) return -1;
   *total = sum + (hs->n_shoot_cols ? 2 : 0);
   return 0;
 }
@@ -420,7 +414,7 @@ static int act_heads_pack(const char* who, const ac_act_heads_t* hs, int total, 
 int64_t ac_act_eval_workspace_floats(const ac_act_heads_t* heads, int32_t M) {
   int total;
   if (act_heads_ok("ac_act_eval_workspace_floats", heads, M, &total)) return -1;
-  return (int64_t)mlpt::bwd_workgroups(M) * (mlpt::H + 1) * total;
+  return (int64_t)trn::capped_tiles(M, mlpt::RT, mlpt::BWD_WGS) * (mlpt::H + 1) * total;
 }
 
 int ac_act_eval_forward(int32_t device_id, void* stream, const ac_act_heads_t* heads, int32_t M, const float* d_x, const float* const* d_w,
@@ -434,8 +428,7 @@ int ac_act_eval_forward(int32_t device_id, void* stream, const ac_act_heads_t* h
   actt::Heads hd;
   if (act_heads_pack(who, heads, total, d_w, d_b, nullptr, nullptr, &hd, nullptr)) return -1;
   HIP_OK(hipSetDevice(device_id));
-  const int ntiles = (M + mlpt::RT - 1) / mlpt::RT;
-  const dim3 grid(ntiles < mlpt::FWD_WGS ? ntiles : mlpt::FWD_WGS), block(512);
+  const dim3 grid(trn::capped_tiles(M, mlpt::RT, mlpt::FWD_WGS)), block(512);
   const int vec = mlp_vec(d_x, mlpt::H, mlpt::H);
   if (total <= 128)
     hipLaunchKernelGGL(actt::act_eval_fwd<1>, grid, block, 0, (hipStream_t)stream, d_x, hd, d_actions, d_alpha0, d_beta0, d_logp, d_ent, (int)M, vec);
@@ -457,7 +450,7 @@ int ac_act_eval_backward(int32_t device_id, void* stream, const ac_act_heads_t* 
   actt::Grads gr;
   if (act_heads_pack(who, heads, total, d_w, d_b, d_dw, d_db, &hd, &gr)) return -1;
   HIP_OK(hipSetDevice(device_id));
-  const int G = mlpt::bwd_workgroups(M);
+  const int G = trn::capped_tiles(M, mlpt::RT, mlpt::BWD_WGS);
   const dim3 grid(G), block(512);
   const int vec = mlp_vec(d_x, mlpt::H, mlpt::H);
 #define AC_ACT_BWD(SPW)                                                                                                                       \

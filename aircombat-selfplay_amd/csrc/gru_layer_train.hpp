@@ -61,9 +61,6 @@ __device__ __forceinline__ void store_rows(const float (&v)[RT * W / 512], float
   }
 }
 
-inline int tiles(int M) { return (M + RT - 1) / RT; }
-inline int capped(int M, int cap) { return tiles(M) < cap ? tiles(M) : cap; }
-
 // gi [M, 384] = x [M, 128] W_ihᵀ + b_ih. Wave w owns gate columns 48 w .. 48 w + 47 (three 16-column tiles, so a row of its results is
 // 192 contiguous bytes): B[j][s] = W_ih[48 w + 16 j + n][k = 32 q + s].
 __global__ __launch_bounds__(512) void gru_gi_fwd(const float* __restrict__ x, const float* __restrict__ wih, const float* __restrict__ bih,
@@ -331,21 +328,13 @@ __global__ __launch_bounds__(512) void gru_dx(const float* __restrict__ dgi, con
   }
 }
 
-// out[e] = the sum over the S partial sets of ws[s * nel + e], in an order fixed by S alone: eight interleaved running sums, then a
-// tree. blockIdx.y picks the family (gru_dw's two gradients): its sets start at ws + y * S * nel, its results go to o0 (the first n0
+// out[e] = the sum over the S partial sets of ws[s * nel + e] (trn::sum_sets). blockIdx.y picks the family (gru_dw's two gradients): its sets start at ws + y * S * nel, its results go to o0 (the first n0
 // elements of a set) and o1 (the rest), or to p0 and p1 for y = 1.
 __global__ __launch_bounds__(256) void gru_sum_partials(const float* __restrict__ ws, int S, int nel, int n0, float* __restrict__ o0,
                                                         float* __restrict__ o1, float* __restrict__ p0, float* __restrict__ p1) {
   const int e = blockIdx.x * 256 + threadIdx.x;
   if (e >= nel) return;
-  ws += (size_t)blockIdx.y * S * nel;
-  float a[8] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-  int s = 0;
-  for (; s + 8 <= S; s += 8)
-#pragma unroll
-    for (int j = 0; j < 8; ++j) a[j] += ws[(size_t)(s + j) * nel + e];
-  for (int j = 0; s < S; ++s, ++j) a[j] += ws[(size_t)s * nel + e];
-  const float r = ((a[0] + a[1]) + (a[2] + a[3])) + ((a[4] + a[5]) + (a[6] + a[7]));
+  const float r = trn::sum_sets(ws + (size_t)blockIdx.y * S * nel, S, nel, e);
   float* d0 = blockIdx.y ? p0 : o0;
   float* d1 = blockIdx.y ? p1 : o1;
   if (e < n0) d0[e] = r;
@@ -359,8 +348,8 @@ struct Layout {
 };
 inline Layout layout(int M) {
   Layout l;
-  l.dw_sets = capped(M, DW_WGS / 2);
-  l.ln_sets = capped(M, LNB_WGS);
+  l.dw_sets = trn::capped_tiles(M, RT, DW_WGS / 2);
+  l.ln_sets = trn::capped_tiles(M, RT, LNB_WGS);
   l.dgh = (int64_t)M * G;
   l.dy = l.dgh + (int64_t)M * G;
   l.dwp = l.dy + (int64_t)M * H;
@@ -372,16 +361,7 @@ inline Layout layout(int M) {
 
 // ------------------------------------------------------------------------------------------------ C ABI (include/aircombat.h)
 extern "C" {
-static int gru_layer_shape_ok(const char* who, int32_t N, int32_t T) {
-  if (N < 1 || T < 1) return fail(std::string(who) + ": N and T must be at least 1");
-  if ((int64_t)N * T > (int64_t)INT32_MAX - 2 * grul::RT) return fail(std::string(who) + ": N * T exceeds the kernels' 32-bit row index");
-  return 0;
-}
-static bool gru_layer_aligned(std::initializer_list<const void*> ps) {
-  for (const void* p : ps)
-    if ((uintptr_t)p & 15) return false;
-  return true;
-}
+static int gru_layer_shape_ok(const char* who, int32_t N, int32_t T) { return gru_shape_ok(who, N, T, 2 * grul::RT); }
 
 int64_t ac_gru_layer_workspace_floats(int32_t N, int32_t T) {
   if (gru_layer_shape_ok("ac_gru_layer_workspace_floats", N, T)) return -1;
@@ -408,17 +388,17 @@ int ac_gru_layer_forward(int32_t device_id, void* stream, int32_t N, int32_t T, 
     return fail("ac_gru_layer_forward: null argument");
   if ((d_saved == nullptr) != (d_stats == nullptr)) return fail("ac_gru_layer_forward: saved and stats go together (both, or both NULL)");
   if (gru_layer_shape_ok("ac_gru_layer_forward", N, T)) return -1;
-  if (!gru_layer_aligned({d_x, d_w_ih, d_gamma, d_beta, d_workspace, d_out, d_y, d_stats}))
+  if (!trn::aligned16({d_x, d_w_ih, d_gamma, d_beta, d_workspace, d_out, d_y, d_stats}))
     return fail("ac_gru_layer_forward: x, w_ih, gamma, beta, workspace, out, y and stats must be 16-byte aligned");
   HIP_OK(hipSetDevice(device_id));
   const int M = N * T;
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(grul::gru_gi_fwd, dim3(grul::capped(M, grul::GI_WGS)), dim3(512), 0, s, d_x, d_w_ih, d_b_ih, d_workspace, M);
+  hipLaunchKernelGGL(grul::gru_gi_fwd, dim3(trn::capped_tiles(M, grul::RT, grul::GI_WGS)), dim3(512), 0, s, d_x, d_w_ih, d_b_ih, d_workspace, M);
   HIP_OK(hipGetLastError());
-  hipLaunchKernelGGL(grut::gru_seq_fwd, dim3((N + grut::RT - 1) / grut::RT), dim3(512), 0, s, (const float*)d_workspace, d_hxs, d_masks, d_w_hh,
+  hipLaunchKernelGGL(grut::gru_seq_fwd, dim3(trn::tiles(N, grut::RT)), dim3(512), 0, s, (const float*)d_workspace, d_hxs, d_masks, d_w_hh,
                      d_b_hh, d_y, d_h_T, d_saved, (int)N, (int)T);
   HIP_OK(hipGetLastError());
-  hipLaunchKernelGGL(grul::gru_ln_fwd, dim3(grul::capped(M, grul::LN_WGS)), dim3(512), 0, s, (const float*)d_y, d_gamma, d_beta, d_out, d_stats, M, eps);
+  hipLaunchKernelGGL(grul::gru_ln_fwd, dim3(trn::capped_tiles(M, grul::RT, grul::LN_WGS)), dim3(512), 0, s, (const float*)d_y, d_gamma, d_beta, d_out, d_stats, M, eps);
   HIP_OK(hipGetLastError());
   return 0;
 }
@@ -431,7 +411,7 @@ int ac_gru_layer_backward(int32_t device_id, void* stream, int32_t N, int32_t T,
       !d_db_ih || !d_db_hh || !d_dgamma || !d_dbeta)
     return fail("ac_gru_layer_backward: null argument");
   if (gru_layer_shape_ok("ac_gru_layer_backward", N, T)) return -1;
-  if (!gru_layer_aligned({d_g_out, d_x, d_hxs, d_gamma, d_y, d_stats, d_workspace, d_dx}))
+  if (!trn::aligned16({d_g_out, d_x, d_hxs, d_gamma, d_y, d_stats, d_workspace, d_dx}))
     return fail("ac_gru_layer_backward: g_out, x, hxs, gamma, y, stats, workspace and dx must be 16-byte aligned");
   HIP_OK(hipSetDevice(device_id));
   const int M = N * T;
@@ -448,7 +428,7 @@ int ac_gru_layer_backward(int32_t device_id, void* stream, int32_t N, int32_t T,
     HIP_OK(hipMemsetAsync(d_dgamma, 0, grul::H * sizeof(float), s));
     HIP_OK(hipMemsetAsync(d_dbeta, 0, grul::H * sizeof(float), s));
   }
-  hipLaunchKernelGGL(grut::gru_seq_bwd, dim3((N + grut::RT - 1) / grut::RT), dim3(512), 0, s, d_g_out ? (const float*)dy : nullptr, d_g_h_T, d_saved,
+  hipLaunchKernelGGL(grut::gru_seq_bwd, dim3(trn::tiles(N, grut::RT)), dim3(512), 0, s, d_g_out ? (const float*)dy : nullptr, d_g_h_T, d_saved,
                      d_y, d_hxs, d_masks, d_w_hh, dgi, dgh, d_dhxs, (int)N, (int)T);
   HIP_OK(hipGetLastError());
   hipLaunchKernelGGL(grul::gru_dw, dim3(2 * l.dw_sets), dim3(512), 0, s, (const float*)dgi, (const float*)dgh, d_x, d_hxs, d_y, d_masks, dwp, (int)N, M);
@@ -457,7 +437,7 @@ int ac_gru_layer_backward(int32_t device_id, void* stream, int32_t N, int32_t T,
                      grul::G * grul::H, d_dw_ih, d_db_ih, d_dw_hh, d_db_hh);
   HIP_OK(hipGetLastError());
   if (d_dx) {
-    hipLaunchKernelGGL(grul::gru_dx, dim3(grul::capped(M, grul::DX_WGS)), dim3(512), 0, s, (const float*)dgi, d_w_ih, d_dx, M);
+    hipLaunchKernelGGL(grul::gru_dx, dim3(trn::capped_tiles(M, grul::RT, grul::DX_WGS)), dim3(512), 0, s, (const float*)dgi, d_w_ih, d_dx, M);
     HIP_OK(hipGetLastError());
   }
   return 0;

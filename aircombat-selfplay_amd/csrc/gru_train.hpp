@@ -184,9 +184,10 @@ __global__ __launch_bounds__(512) void gru_seq_bwd(const float* __restrict__ dy,
 
 // ------------------------------------------------------------------------------------------------ C ABI (include/aircombat.h)
 extern "C" {
-static int gru_shape_ok(const char* who, int32_t N, int32_t T) {
+// slack: the rows past N * T that a kernel's tile may index before its bounds test (gru_layer_train.hpp walks 32-row tiles)
+static int gru_shape_ok(const char* who, int32_t N, int32_t T, int slack = grut::RT) {
   if (N < 1 || T < 1) return fail(std::string(who) + ": N and T must be at least 1");
-  if ((int64_t)N * T > (int64_t)INT32_MAX - grut::RT) return fail(std::string(who) + ": N * T exceeds the kernels' 32-bit row index");
+  if ((int64_t)N * T > (int64_t)INT32_MAX - slack) return fail(std::string(who) + ": N * T exceeds the kernels' 32-bit row index");
   return 0;
 }
 int ac_gru_seq_forward(int32_t device_id, void* stream, int32_t N, int32_t T, const float* d_gi, const float* d_hxs, const float* d_masks,
@@ -194,7 +195,7 @@ int ac_gru_seq_forward(int32_t device_id, void* stream, int32_t N, int32_t T, co
   if (!d_gi || !d_hxs || !d_masks || !d_w_hh || !d_b_hh || !d_y || !d_h_T) return fail("ac_gru_seq_forward: null argument");
   if (gru_shape_ok("ac_gru_seq_forward", N, T)) return -1;
   HIP_OK(hipSetDevice(device_id));
-  hipLaunchKernelGGL(grut::gru_seq_fwd, dim3((N + grut::RT - 1) / grut::RT), dim3(512), 0, (hipStream_t)stream, d_gi, d_hxs, d_masks,
+  hipLaunchKernelGGL(grut::gru_seq_fwd, dim3(trn::tiles(N, grut::RT)), dim3(512), 0, (hipStream_t)stream, d_gi, d_hxs, d_masks,
                      d_w_hh, d_b_hh, d_y, d_h_T, d_saved, (int)N, (int)T);
   HIP_OK(hipGetLastError());
   return 0;
@@ -205,7 +206,7 @@ int ac_gru_seq_backward(int32_t device_id, void* stream, int32_t N, int32_t T, c
   if (!d_saved || !d_y || !d_hxs || !d_masks || !d_w_hh || !d_dgi || !d_dgh) return fail("ac_gru_seq_backward: null argument");
   if (gru_shape_ok("ac_gru_seq_backward", N, T)) return -1;
   HIP_OK(hipSetDevice(device_id));
-  hipLaunchKernelGGL(grut::gru_seq_bwd, dim3((N + grut::RT - 1) / grut::RT), dim3(512), 0, (hipStream_t)stream, d_dy, d_dh_T, d_saved, d_y,
+  hipLaunchKernelGGL(grut::gru_seq_bwd, dim3(trn::tiles(N, grut::RT)), dim3(512), 0, (hipStream_t)stream, d_dy, d_dh_T, d_saved, d_y,
                      d_hxs, d_masks, d_w_hh, d_dgi, d_dgh, d_dhxs, (int)N, (int)T);
   HIP_OK(hipGetLastError());
   return 0;

@@ -323,29 +323,18 @@ __global__ __launch_bounds__(512) void mlp_block_bwd(const float* __restrict__ d
   }
 }
 
-// dW, db, dgamma, dbeta = the sum of the G partial sets, in an order fixed by G alone: eight interleaved running sums, then a tree
+// dW, db, dgamma, dbeta = the sum of the G partial sets (trn::sum_sets)
 __global__ __launch_bounds__(256) void mlp_block_reduce(const float* __restrict__ ws, int G, int K, float* __restrict__ dw, float* __restrict__ db,
                                                         float* __restrict__ dgamma, float* __restrict__ dbeta) {
   const int nel = H * K + 3 * H;
   const int e = blockIdx.x * 256 + threadIdx.x;
   if (e >= nel) return;
-  float a[8] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-  int g = 0;
-  for (; g + 8 <= G; g += 8)
-#pragma unroll
-    for (int j = 0; j < 8; ++j) a[j] += ws[(size_t)(g + j) * nel + e];
-  for (int j = 0; g < G; ++g, ++j) a[j] += ws[(size_t)g * nel + e];
-  const float s = ((a[0] + a[1]) + (a[2] + a[3])) + ((a[4] + a[5]) + (a[6] + a[7]));
+  const float s = trn::sum_sets(ws, G, nel, e);
   const int v = e - H * K;
   if (v < 0) dw[e] = s;
   else if (v < H) db[v] = s;
   else if (v < 2 * H) dgamma[v - H] = s;
   else dbeta[v - 2 * H] = s;
-}
-
-inline int bwd_workgroups(int M) {
-  const int ntiles = (M + RT - 1) / RT;
-  return ntiles < BWD_WGS ? ntiles : BWD_WGS;
 }
 }  // namespace mlpt
 
@@ -354,15 +343,14 @@ extern "C" {
 static int mlp_shape_ok(const char* who, int32_t M, int32_t K) {
   if (M < 1) return fail(std::string(who) + ": M must be at least 1");
   if (K < 1 || K > mlpt::KMAX) return fail(std::string(who) + ": K must be 1 .. 256");
-  if ((int64_t)M * mlpt::H > (int64_t)INT32_MAX - mlpt::RT * mlpt::H) return fail(std::string(who) + ": M * 128 exceeds the kernels' 32-bit index");
-  return 0;
+  return trn::rows_fit_i32(who, M, mlpt::H, mlpt::RT);
 }
 static int mlp_kp(int32_t K) { return K <= 16 ? 16 : K <= 32 ? 32 : K <= 64 ? 64 : K <= 128 ? 128 : 256; }
-static int mlp_vec(const void* p, int32_t K, int kp) { return K == kp && kp >= 64 && ((uintptr_t)p & 15) == 0; }
+static int mlp_vec(const void* p, int32_t K, int kp) { return K == kp && kp >= 64 && trn::aligned16(p); }
 
 int64_t ac_mlp_block_workspace_floats(int32_t M, int32_t K) {
   if (mlp_shape_ok("ac_mlp_block_workspace_floats", M, K)) return -1;
-  return (int64_t)mlpt::bwd_workgroups(M) * (mlpt::H * K + 3 * mlpt::H);
+  return (int64_t)trn::capped_tiles(M, mlpt::RT, mlpt::BWD_WGS) * (mlpt::H * K + 3 * mlpt::H);
 }
 
 int ac_mlp_block_forward(int32_t device_id, void* stream, int32_t M, int32_t K, float eps, const float* d_x, const float* d_w, const float* d_b,
@@ -370,8 +358,8 @@ int ac_mlp_block_forward(int32_t device_id, void* stream, int32_t M, int32_t K, 
   if (!d_x || !d_w || !d_b || !d_gamma || !d_beta || !d_y) return fail("ac_mlp_block_forward: null argument");
   if (mlp_shape_ok("ac_mlp_block_forward", M, K)) return -1;
   HIP_OK(hipSetDevice(device_id));
-  const int kp = mlp_kp(K), ntiles = (M + mlpt::RT - 1) / mlpt::RT;
-  const dim3 grid(ntiles < mlpt::FWD_WGS ? ntiles : mlpt::FWD_WGS), block(512);
+  const int kp = mlp_kp(K);
+  const dim3 grid(trn::capped_tiles(M, mlpt::RT, mlpt::FWD_WGS)), block(512);
   const int vec = mlp_vec(d_x, K, kp);
 #define AC_MLP_FWD(KP)                                                                                                                      \
   hipLaunchKernelGGL(mlpt::mlp_block_fwd<KP>, grid, block, 0, (hipStream_t)stream, d_x, d_w, d_b, d_gamma, d_beta, d_y, d_stats, (int)M, \
@@ -395,7 +383,7 @@ int ac_mlp_block_backward(int32_t device_id, void* stream, int32_t M, int32_t K,
     return fail("ac_mlp_block_backward: null argument");
   if (mlp_shape_ok("ac_mlp_block_backward", M, K)) return -1;
   HIP_OK(hipSetDevice(device_id));
-  const int kp = mlp_kp(K), G = mlpt::bwd_workgroups(M);
+  const int kp = mlp_kp(K), G = trn::capped_tiles(M, mlpt::RT, mlpt::BWD_WGS);
   const dim3 grid(G), block(512);
   const int vecx = mlp_vec(d_x, K, kp), vecdy = mlp_vec(d_dy, mlpt::H, mlpt::H);
 #define AC_MLP_BWD(KP)                                                                                                                        \

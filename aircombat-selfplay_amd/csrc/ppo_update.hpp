@@ -166,8 +166,6 @@ __device__ __forceinline__ int entry_of(const Entry* __restrict__ tab, int n, in
   return lo;
 }
 
-__device__ __forceinline__ bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 // one workgroup per chunk: the sum of squares of its gradients to ws[c], its group (as a float) to ws[nchunks + c]
 __global__ __launch_bounds__(THREADS) void grad_sq_chunks(const Entry* __restrict__ tab, int n, int nchunks, float* __restrict__ ws) {
   __shared__ float sh[4];
@@ -176,7 +174,7 @@ __global__ __launch_bounds__(THREADS) void grad_sq_chunks(const Entry* __restric
   const int64_t off = (int64_t)(c - e.first_chunk) * CHUNK;
   const int len = (int)(e.numel - off < CHUNK ? e.numel - off : CHUNK);
   const float* g = e.g + off;
-  const bool vec = aligned16(g);
+  const bool vec = trn::aligned16(g);
   float s = 0.0f;
 #pragma unroll
   for (int j = 0; j < CHUNK / (4 * THREADS); ++j) {
@@ -230,7 +228,7 @@ __global__ __launch_bounds__(THREADS) void clip_adam_chunks(const Entry* __restr
   const float coef = clip ? (q > 1.0f ? 1.0f : q) : 1.0f;
   const float w1 = (float)(1.0 - e.beta1), b2 = (float)e.beta2, w2 = (float)(1.0 - e.beta2);
   const float step_size = (float)(e.lr / e.bias_correction1), bc2_sqrt = (float)sqrt(e.bias_correction2), eps = (float)e.eps;
-  const bool vec = aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v);
+  const bool vec = trn::aligned16(p) && trn::aligned16(g) && trn::aligned16(m) && trn::aligned16(v);
 #pragma unroll
   for (int j = 0; j < CHUNK / (4 * THREADS); ++j) {
     const int i = 4 * (j * THREADS + threadIdx.x);

@@ -9,17 +9,11 @@ stream. It has the same children (``gru``, ``norm``), so the same Parameter obje
 put there, for a ``DeviceFusedGRULayer`` holding the same two submodules. Nothing selects it unless the caller asks.
 """
 import torch
-import torch.nn as nn
 
-from . import capi
 from . import gru_train
 from .gru_train import HID, SAVED, DeviceGRULayer
 from .policy import UnsupportedPolicy
-
-
-def _call(what, rc, lib):
-    if rc != 0:
-        raise RuntimeError(f"{what} failed: {lib.last_error()}")
+from .train_common import Launch, layernorm_faults, swap_children
 
 
 class DeviceGRULayerFunction(torch.autograd.Function):
@@ -33,22 +27,15 @@ class DeviceGRULayerFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, hxs, masks, w_ih, w_hh, b_ih, b_hh, gamma, beta, eps, save):
-        lib = capi.load_library()
         N = hxs.shape[0]
         T = x.shape[0] // N
-        dev = x.device
         x, hxs, masks, w_ih, w_hh, b_ih, b_hh, gamma, beta = (t.contiguous() for t in (x, hxs, masks, w_ih, w_hh, b_ih, b_hh, gamma, beta))
-        new = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)
+        run = Launch(x)
         # the gate pre-activations live in a torch tensor: torch's allocator orders its reuse on this stream
-        ws = new(T * N * 3 * HID)
-        out, h_T, y = new(T * N, HID), new(N, HID), new(T * N, HID)
-        saved, stats = (new(T * N, SAVED), new(T * N, 2)) if save else (None, None)
-        ptr = lambda t: None if t is None else t.data_ptr()
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        _call("ac_gru_layer_forward", lib.ac_gru_layer_forward(dev.index, stream, N, T, x.data_ptr(), hxs.data_ptr(), masks.data_ptr(),
-                                                               w_ih.data_ptr(), w_hh.data_ptr(), b_ih.data_ptr(), b_hh.data_ptr(),
-                                                               gamma.data_ptr(), beta.data_ptr(), eps, ws.data_ptr(), out.data_ptr(),
-                                                               h_T.data_ptr(), y.data_ptr(), ptr(saved), ptr(stats)), lib)
+        ws = run.empty(T * N * 3 * HID)
+        out, h_T, y = run.empty(T * N, HID), run.empty(N, HID), run.empty(T * N, HID)
+        saved, stats = (run.empty(T * N, SAVED), run.empty(T * N, 2)) if save else (None, None)
+        run("ac_gru_layer_forward", N, T, x, hxs, masks, w_ih, w_hh, b_ih, b_hh, gamma, beta, eps, ws, out, h_T, y, saved, stats)
         if save:
             ctx.save_for_backward(x, hxs, masks, w_ih, w_hh, gamma, y, saved, stats)
             ctx.shape = (N, T)
@@ -57,25 +44,19 @@ class DeviceGRULayerFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_out, g_h):
-        lib = capi.load_library()
         x, hxs, masks, w_ih, w_hh, gamma, y, saved, stats = ctx.saved_tensors
         N, T = ctx.shape
-        dev = x.device
         need = ctx.needs_input_grad
-        new = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)
-        ws = new(lib.ac_gru_layer_workspace_floats(N, T))
+        run = Launch(x)
+        new = run.empty
+        ws = run.workspace("ac_gru_layer_workspace_floats", N, T)
         dx = new(T * N, HID) if need[0] else None
         dhxs = new(N, HID) if need[1] else None
         dw_ih, dw_hh, db_ih, db_hh, dgamma, dbeta = new(3 * HID, HID), new(3 * HID, HID), new(3 * HID), new(3 * HID), new(HID), new(HID)
         g_out = None if g_out is None else g_out.contiguous()
         g_h = None if g_h is None else g_h.contiguous()
-        ptr = lambda t: None if t is None else t.data_ptr()
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        _call("ac_gru_layer_backward", lib.ac_gru_layer_backward(dev.index, stream, N, T, ptr(g_out), ptr(g_h), x.data_ptr(), hxs.data_ptr(),
-                                                                 masks.data_ptr(), w_ih.data_ptr(), w_hh.data_ptr(), gamma.data_ptr(),
-                                                                 y.data_ptr(), saved.data_ptr(), stats.data_ptr(), ws.data_ptr(), ptr(dx),
-                                                                 ptr(dhxs), dw_ih.data_ptr(), dw_hh.data_ptr(), db_ih.data_ptr(),
-                                                                 db_hh.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr()), lib)
+        run("ac_gru_layer_backward", N, T, g_out, g_h, x, hxs, masks, w_ih, w_hh, gamma, y, saved, stats, ws, dx, dhxs, dw_ih, dw_hh, db_ih,
+            db_hh, dgamma, dbeta)
         grads = (dx, dhxs, None, dw_ih, dw_hh, db_ih, db_hh, dgamma, dbeta, None, None)
         return tuple(g if n else None for g, n in zip(grads, need))
 
@@ -100,19 +81,7 @@ def check_layer(gru, norm, where="rnn"):
         gru_train.check_gru(gru, where + ".gru")
     except UnsupportedPolicy as exc:
         said.append(str(exc))
-    bad = []
-    if not isinstance(norm, nn.LayerNorm):
-        bad.append(f"not an nn.LayerNorm ({type(norm).__name__})")
-    else:
-        if tuple(norm.normalized_shape) != (HID,):
-            bad.append(f"LayerNorm over {tuple(norm.normalized_shape)} (only ({HID},))")
-        if norm.weight is None or norm.bias is None:
-            bad.append("LayerNorm without affine parameters")
-        for name, p in norm.named_parameters():
-            if p.dtype != torch.float32:
-                bad.append(f"{name} dtype {p.dtype} (only float32)")
-            if p.device.type != "cuda":
-                bad.append(f"{name} device {p.device} (only a CUDA device)")
+    bad = layernorm_faults(norm)
     if bad:
         said.append(f"{where}.norm: " + ", ".join(bad))
     if said:
@@ -147,22 +116,7 @@ def use_device_gru_layer(module):
     DeviceGRULayer that use_device_gru put there, for a DeviceFusedGRULayer holding the same two submodules. ``module`` is an nn.Module
     (``policy.actor``, ``policy.critic``) or an object with ``actor`` / ``critic`` modules. Every layer is checked before any is
     swapped; an unsupported one raises UnsupportedPolicy naming it. Returns the number of layers swapped."""
-    roots = [(module, "")] if isinstance(module, nn.Module) else \
-        [(getattr(module, k), k + ".") for k in ("actor", "critic") if isinstance(getattr(module, k, None), nn.Module)]
-    if not roots:
-        raise UnsupportedPolicy(f"{type(module).__name__}: neither an nn.Module nor an object with actor / critic modules")
-    found = []
-    for root, prefix in roots:
-        if _swappable(root):
-            raise UnsupportedPolicy(f"{prefix or type(root).__name__}: a GRULayer itself cannot be swapped in place; pass the module holding it")
-        for pname, parent in root.named_modules():
-            for cname, child in parent.named_children():
-                if _swappable(child):
-                    found.append((parent, cname, child, prefix + (pname + "." if pname else "") + cname))
-    for _, _, child, where in found:
+    def check(child, where):
         check_layer(child.gru, child.norm, where)
-        if getattr(child, "_num_layers", 1) != 1:
-            raise UnsupportedPolicy(f"{where}: {child._num_layers} layers (only 1)")
-    for parent, cname, child, _ in found:
-        setattr(parent, cname, DeviceFusedGRULayer(child.gru.input_size, child.gru.hidden_size, child.gru.num_layers, gru=child.gru, norm=child.norm))
-    return len(found)
+        gru_train.check_one_layer(child, where)
+    return swap_children(module, _swappable, check, lambda child: gru_train.same_children(DeviceFusedGRULayer, child), "a GRULayer")

@@ -11,16 +11,11 @@ submodules, so Parameter objects, optimiser state and checkpoints are unchanged.
 import torch
 import torch.nn as nn
 
-from . import capi
 from .policy import UnsupportedPolicy
+from .train_common import Launch, swap_children
 
 HID = 128
 SAVED = 4 * HID   # floats per (step, row) the forward keeps for the backward: r, z, n, W_hn h + b_hn
-
-
-def _call(what, rc, lib):
-    if rc != 0:
-        raise RuntimeError(f"{what} failed: {lib.last_error()}")
 
 
 class DeviceGRUFunction(torch.autograd.Function):
@@ -32,19 +27,14 @@ class DeviceGRUFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, hxs, masks, w_ih, w_hh, b_ih, b_hh, save):
-        lib = capi.load_library()
         N = hxs.shape[0]
         T = x.shape[0] // N
-        dev = x.device
         x, hxs, masks, w_hh, b_hh = x.contiguous(), hxs.contiguous(), masks.contiguous(), w_hh.contiguous(), b_hh.contiguous()
         gi = torch.addmm(b_ih, x, w_ih.t())
-        y = torch.empty((T * N, HID), dtype=torch.float32, device=dev)
-        h_T = torch.empty((N, HID), dtype=torch.float32, device=dev)
-        saved =torch.empty((T * N, SAVED), dtype=torch.float32, device=dev) if save else None
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        _call("ac_gru_seq_forward", lib.ac_gru_seq_forward(dev.index, stream, N, T, gi.data_ptr(), hxs.data_ptr(), masks.data_ptr(),
-                                                           w_hh.data_ptr(), b_hh.data_ptr(), y.data_ptr(), h_T.data_ptr(),
-                                                           None if saved is None else saved.data_ptr()), lib)
+        run = Launch(x)
+        y, h_T = run.empty(T * N, HID), run.empty(N, HID)
+        saved = run.empty(T * N, SAVED) if save else None
+        run("ac_gru_seq_forward", N, T, gi, hxs, masks, w_hh, b_hh, y, h_T, saved)
         if save:
             ctx.save_for_backward(x, hxs, masks, w_ih, w_hh, y, saved)
             ctx.shape = (N, T)
@@ -53,21 +43,15 @@ class DeviceGRUFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy, dh_T):
-        lib = capi.load_library()
         x, hxs, masks, w_ih, w_hh, y, saved = ctx.saved_tensors
         N, T = ctx.shape
-        dev = x.device
         need = ctx.needs_input_grad
-        dgi = torch.empty((T * N, 3 * HID), dtype=torch.float32, device=dev)
-        dgh = torch.empty((T * N, 3 * HID), dtype=torch.float32, device=dev)
-        dhxs = torch.empty((N, HID), dtype=torch.float32, device=dev) if need[1] else None
+        run = Launch(x)
+        dgi, dgh = run.empty(T * N, 3 * HID), run.empty(T * N, 3 * HID)
+        dhxs = run.empty(N, HID) if need[1] else None
         dy = None if dy is None else dy.contiguous()
         dh_T = None if dh_T is None else dh_T.contiguous()
-        ptr = lambda t: None if t is None else t.data_ptr()
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        _call("ac_gru_seq_backward", lib.ac_gru_seq_backward(dev.index, stream, N, T, ptr(dy), ptr(dh_T), saved.data_ptr(), y.data_ptr(),
-                                                             hxs.data_ptr(), masks.data_ptr(), w_hh.data_ptr(), dgi.data_ptr(),
-                                                             dgh.data_ptr(), ptr(dhxs)), lib)
+        run("ac_gru_seq_backward", N, T, dy, dh_T, saved, y, hxs, masks, w_hh, dgi, dgh, dhxs)
         dx = dgi @ w_ih if need[0] else None
         # the weight gradients as one batched GEMM over the steps (K = N each) and a sum over T: a single GEMM with K = T * N
         # accumulates in fp32 along the whole minibatch (measured 6.1e-6 relative against float64 at N = 4096, T = 60, torch's
@@ -144,6 +128,16 @@ class DeviceGRULayer(nn.Module):
         return self._hidden_size
 
 
+def check_one_layer(layer, where):
+    if getattr(layer, "_num_layers", 1) != 1:
+        raise UnsupportedPolicy(f"{where}: {layer._num_layers} layers (only 1)")
+
+
+def same_children(cls, layer):
+    """``cls`` (DeviceGRULayer or a subclass) holding the very ``gru`` and ``norm`` of ``layer``."""
+    return cls(layer.gru.input_size, layer.gru.hidden_size, layer.gru.num_layers, gru=layer.gru, norm=layer.norm)
+
+
 def _gru_layer_shaped(m):
     return not isinstance(m, DeviceGRULayer) and isinstance(getattr(m, "gru", None), nn.GRU) and isinstance(getattr(m, "norm", None), nn.LayerNorm)
 
@@ -153,22 +147,7 @@ def use_device_gru(module):
     DeviceGRULayer holding the same two submodules. ``module`` is an nn.Module (``policy.actor``, ``policy.critic``) or an object with
     ``actor`` / ``critic`` modules (the reference's PPO and MAPPO ``PPOPolicy``). Every layer is checked before any is swapped; an
     unsupported one raises UnsupportedPolicy naming it. Returns the number of layers swapped."""
-    roots = [(module, "")] if isinstance(module, nn.Module) else \
-        [(getattr(module, k), k + ".") for k in ("actor", "critic") if isinstance(getattr(module, k, None), nn.Module)]
-    if not roots:
-        raise UnsupportedPolicy(f"{type(module).__name__}: neither an nn.Module nor an object with actor / critic modules")
-    found = []
-    for root, prefix in roots:
-        if _gru_layer_shaped(root):
-            raise UnsupportedPolicy(f"{prefix or type(root).__name__}: a GRULayer itself cannot be swapped in place; pass the module holding it")
-        for pname, parent in root.named_modules():
-            for cname, child in parent.named_children():
-                if _gru_layer_shaped(child):
-                    found.append((parent, cname, child, prefix + (pname + "." if pname else "") + cname))
-    for _, _, child, where in found:
+    def check(child, where):
         check_gru(child.gru, where + ".gru")
-        if getattr(child, "_num_layers", 1) != 1:
-            raise UnsupportedPolicy(f"{where}: {child._num_layers} layers (only 1)")
-    for parent, cname, child, _ in found:
-        setattr(parent, cname, DeviceGRULayer(child.gru.input_size, child.gru.hidden_size, child.gru.num_layers, gru=child.gru, norm=child.norm))
-    return len(found)
+        check_one_layer(child, where)
+    return swap_children(module, _gru_layer_shaped, check, lambda child: same_children(DeviceGRULayer, child), "a GRULayer")

@@ -12,16 +12,11 @@ Parameter objects, optimiser state and checkpoints are unchanged. It composes wi
 import torch
 import torch.nn as nn
 
-from . import capi
 from .policy import UnsupportedPolicy
+from .train_common import Launch, layernorm_faults, linear_faults, swap_children
 
 HID = 128      # out-features of every block, the LayerNorm's width
 K_MAX = 256    # in-features at most
-
-
-def _call(what, rc, lib):
-    if rc != 0:
-        raise RuntimeError(f"{what} failed: {lib.last_error()}")
 
 
 class DeviceMLPBlockFunction(torch.autograd.Function):
@@ -33,37 +28,26 @@ class DeviceMLPBlockFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, w, b, gamma, beta, eps, save):
-        lib = capi.load_library()
         x, w, b, gamma, beta = x.contiguous(), w.contiguous(), b.contiguous(), gamma.contiguous(), beta.contiguous()
         M, K = x.shape
-        dev = x.device
-        y = torch.empty((M, HID), dtype=torch.float32, device=dev)
-        stats = torch.empty((M, 2), dtype=torch.float32, device=dev) if save else None
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        _call("ac_mlp_block_forward", lib.ac_mlp_block_forward(dev.index, stream, M, K, eps, x.data_ptr(), w.data_ptr(), b.data_ptr(),
-                                                               gamma.data_ptr(), beta.data_ptr(), y.data_ptr(),
-                                                               None if stats is None else stats.data_ptr()), lib)
+        run = Launch(x)
+        y = run.empty(M, HID)
+        stats = run.empty(M, 2) if save else None
+        run("ac_mlp_block_forward", M, K, eps, x, w, b, gamma, beta, y, stats)
         if save:
             ctx.save_for_backward(x, w, b, gamma, stats)
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        lib = capi.load_library()
         x, w, b, gamma, stats = ctx.saved_tensors
         M, K = x.shape
-        dev = x.device
         dy = dy.contiguous()
-        new = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)
-        # the partial sums live in a torch tensor: torch's allocator orders its reuse on this stream
-        ws = new(lib.ac_mlp_block_workspace_floats(M, K))
-        dx = new(M, K) if ctx.needs_input_grad[0] else None
-        dw, db, dgamma, dbeta = new(HID, K), new(HID), new(HID), new(HID)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        _call("ac_mlp_block_backward", lib.ac_mlp_block_backward(dev.index, stream, M, K, dy.data_ptr(), x.data_ptr(), w.data_ptr(),
-                                                                 b.data_ptr(), gamma.data_ptr(), stats.data_ptr(), ws.data_ptr(),
-                                                                 None if dx is None else dx.data_ptr(), dw.data_ptr(), db.data_ptr(),
-                                                                 dgamma.data_ptr(), dbeta.data_ptr()), lib)
+        run = Launch(x)
+        ws = run.workspace("ac_mlp_block_workspace_floats", M, K)   # the partial sums
+        dx = run.empty(M, K) if ctx.needs_input_grad[0] else None
+        dw, db, dgamma, dbeta = run.empty(HID, K), run.empty(HID), run.empty(HID), run.empty(HID)
+        run("ac_mlp_block_backward", M, K, dy, x, w, b, gamma, stats, ws, dx, dw, db, dgamma, dbeta)
         return dx, dw, db, dgamma, dbeta, None, None
 
 
@@ -79,25 +63,10 @@ def check_block(linear, act, norm, where="fc", device=True):
             bad.append(f"out-features {linear.out_features} (only {HID})")
         if not 1 <= linear.in_features <= K_MAX:
             bad.append(f"in-features {linear.in_features} (at most {K_MAX})")
-        if linear.bias is None:
-            bad.append("Linear without bias")
-        if linear.weight.dtype != torch.float32:
-            bad.append(f"dtype {linear.weight.dtype} (only float32)")
-        if device and linear.weight.device.type != "cuda":
-            bad.append(f"device {linear.weight.device} (only a CUDA device)")
+        bad += linear_faults(linear, device)
     if act is not None and not isinstance(act, nn.ReLU):
         bad.append(f"activation {type(act).__name__} (only ReLU, activation_id 1)")
-    if not isinstance(norm, nn.LayerNorm):
-        bad.append(f"not an nn.LayerNorm ({type(norm).__name__})")
-    else:
-        if tuple(norm.normalized_shape) != (HID,):
-            bad.append(f"LayerNorm over {tuple(norm.normalized_shape)} (only ({HID},))")
-        if norm.weight is None or norm.bias is None:
-            bad.append("LayerNorm without affine parameters")
-        elif norm.weight.dtype != torch.float32:
-            bad.append(f"LayerNorm dtype {norm.weight.dtype} (only float32)")
-        elif device and norm.weight.device.type != "cuda":
-            bad.append(f"LayerNorm device {norm.weight.device} (only a CUDA device)")
+    bad += layernorm_faults(norm, device)
     if bad:
         raise UnsupportedPolicy(f"{where}: " + ", ".join(bad))
 
@@ -176,20 +145,5 @@ def use_device_mlp(module):
     ``module`` for a DeviceMLPLayer holding the very same ``fc``. ``module`` is an nn.Module (``policy.actor``, ``policy.critic``) or
     an object with ``actor`` / ``critic`` modules (the reference's PPO and MAPPO ``PPOPolicy``). Every layer is checked before any is
     swapped; an unsupported one raises UnsupportedPolicy naming it. Returns the number of layers swapped."""
-    roots = [(module, "")] if isinstance(module, nn.Module) else \
-        [(getattr(module, k), k + ".") for k in ("actor", "critic") if isinstance(getattr(module, k, None), nn.Module)]
-    if not roots:
-        raise UnsupportedPolicy(f"{type(module).__name__}: neither an nn.Module nor an object with actor / critic modules")
-    found = []
-    for root, prefix in roots:
-        if _mlp_layer_shaped(root):
-            raise UnsupportedPolicy(f"{prefix or type(root).__name__}: an MLPLayer itself cannot be swapped in place; pass the module holding it")
-        for pname, parent in root.named_modules():
-            for cname, child in parent.named_children():
-                if _mlp_layer_shaped(child):
-                    found.append((parent, cname, child, prefix + (pname + "." if pname else "") + cname))
-    for _, _, child, where in found:
-        check_fc(child.fc, where + ".fc", device=False)
-    for parent, cname, child, _ in found:
-        setattr(parent, cname, DeviceMLPLayer(fc=child.fc))
-    return len(found)
+    return swap_children(module, _mlp_layer_shaped, lambda child, where: check_fc(child.fc, where + ".fc", device=False),
+                         lambda child: DeviceMLPLayer(fc=child.fc), "an MLPLayer")

@@ -16,16 +16,12 @@ import torch
 
 from . import capi
 from .policy import UnsupportedPolicy
+from .train_common import Launch
 
 _ENTRY = np.dtype([("p", "<u8"), ("g", "<u8"), ("m", "<u8"), ("v", "<u8"), ("numel", "<i8"), ("group", "<i4"), ("first_chunk", "<i4"),
                    ("lr", "<f8"), ("eps", "<f8"), ("beta1", "<f8"), ("beta2", "<f8"), ("bias_correction1", "<f8"), ("bias_correction2", "<f8")])
 assert _ENTRY.itemsize == C.sizeof(capi.AcOptimEntry)
 STAT_NAMES = ("loss", "policy_loss", "value_loss", "policy_entropy_loss", "ratio")   # the first entries of the stats vector
-
-
-def _call(what, rc, lib):
-    if rc != 0:
-        raise RuntimeError(f"{what} failed: {lib.last_error()}")
 
 
 def constants():
@@ -42,18 +38,12 @@ class DevicePPOLossFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, values, logp, ent, old_logp, adv, returns, value_preds, active, clip, vcoef, ecoef, clipped):
-        lib = capi.load_library()
-        M, n_ent, dev = logp.numel(), ent.numel(), logp.device
-        new = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)
-        wsf = lib.ac_ppo_loss_workspace_floats(M, n_ent)
-        if wsf < 0:
-            raise RuntimeError(f"ac_ppo_loss_workspace_floats failed: {lib.last_error()}")
-        ws, stats, loss, dlogp, dvalues = new(wsf), new(capi.AC_PPO_NSTAT), new(), new(M), new(M)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        _call("ac_ppo_loss_forward", lib.ac_ppo_loss_forward(
-            dev.index, stream, M, n_ent, old_logp.numel() // M, logp.data_ptr(), old_logp.data_ptr(), adv.data_ptr(), values.data_ptr(), value_preds.data_ptr(),
-            returns.data_ptr(), None if active is None else active.data_ptr(), ent.data_ptr(), clip, vcoef, ecoef, int(clipped),
-            ws.data_ptr(), stats.data_ptr(), loss.data_ptr(), dlogp.data_ptr(), dvalues.data_ptr()), lib)
+        M, n_ent = logp.numel(), ent.numel()
+        run = Launch(logp)
+        ws = run.workspace("ac_ppo_loss_workspace_floats", M, n_ent)
+        stats, loss, dlogp, dvalues = run.empty(capi.AC_PPO_NSTAT), run.empty(), run.empty(M), run.empty(M)
+        run("ac_ppo_loss_forward", M, n_ent, old_logp.numel() // M, logp, old_logp, adv, values, value_preds, returns, active, ent, clip, vcoef,
+            ecoef, int(clipped), ws, stats, loss, dlogp, dvalues)
         ctx.shapes, ctx.ecoef = (values.shape, logp.shape, ent.shape), ecoef
         ctx.save_for_backward(dlogp, dvalues)
         ctx.mark_non_differentiable(stats)
@@ -65,16 +55,13 @@ class DevicePPOLossFunction(torch.autograd.Function):
         none = (None,) * 12
         if g_loss is None:
             return none
-        lib = capi.load_library()
         dlogp, dvalues = ctx.saved_tensors
-        (sv, sl, se), dev = ctx.shapes, dlogp.device
+        sv, sl, se = ctx.shapes
         M, n_ent = dlogp.numel(), int(np.prod(se, dtype=np.int64))
-        g_loss = g_loss.to(device=dev, dtype=torch.float32).contiguous()
-        new = lambda need, s: torch.empty(s, dtype=torch.float32, device=dev) if need else None
-        gv, gl, ge = (new(ctx.needs_input_grad[i], s) for i, s in enumerate((sv, sl, se)))
-        ptr = lambda t: None if t is None else t.data_ptr()
-        _call("ac_ppo_loss_backward", lib.ac_ppo_loss_backward(dev.index, torch.cuda.current_stream(dev).cuda_stream, M, n_ent, g_loss.data_ptr(),
-                                                               dlogp.data_ptr(), dvalues.data_ptr(), ctx.ecoef, ptr(gl), ptr(gv), ptr(ge)), lib)
+        run = Launch(dlogp)
+        g_loss = g_loss.to(device=run.dev, dtype=torch.float32).contiguous()
+        gv, gl, ge = (run.empty(*s) if ctx.needs_input_grad[i] else None for i, s in enumerate((sv, sl, se)))
+        run("ac_ppo_loss_backward", M, n_ent, g_loss, dlogp, dvalues, ctx.ecoef, gl, gv, ge)
         return (gv, gl, ge) + none[3:]
 
 
@@ -162,7 +149,7 @@ def _check_adam(optimizer):
         bad.append(f"{len(todo)} parameters with a gradient (at most {constants()['max_entries']})")
     if bad:
         raise UnsupportedPolicy("device_clip_adam_step: " + "; ".join(bad))
-    return todo, dev
+    return todo
 
 
 def device_clip_adam_step(optimizer, max_grad_norm, clip=True):
@@ -175,12 +162,12 @@ def device_clip_adam_step(optimizer, max_grad_norm, clip=True):
     without a gradient gets no state and no update. Everything is checked before anything is touched; refused with UnsupportedPolicy
     naming the setting: another optimiser class, amsgrad, weight_decay, maximize, capturable, differentiable, a tensor lr, a
     non-float32, non-contiguous or non-CUDA parameter or gradient."""
-    todo, dev = _check_adam(optimizer)
+    todo = _check_adam(optimizer)
     groups = optimizer.param_groups
     if not todo:
         devs = [p.device for g in groups for p in g["params"]]
         return torch.zeros(len(groups), dtype=torch.float32, device=devs[0] if devs else "cpu")
-    lib = capi.load_library()
+    run = Launch(todo[0][1])
     host = torch.empty(len(todo) * _ENTRY.itemsize, dtype=torch.uint8, pin_memory=True)
     tab = host.numpy().view(_ENTRY)
     step_dtype = torch.float64 if torch.get_default_dtype() == torch.float64 else torch.float32
@@ -198,17 +185,12 @@ def device_clip_adam_step(optimizer, max_grad_norm, clip=True):
         tab[i] = (p.data_ptr(), p.grad.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), p.numel(), gi, 0,
                   float(grp["lr"]), float(grp["eps"]), b1, b2, 1.0 - b1 ** step, 1.0 - b2 ** step)
     n, ng = len(todo), len(groups)
-    wsf = lib.ac_optim_workspace_floats(host.data_ptr(), n, ng)   # lays the chunks out in the host table
-    if wsf < 0:
-        raise RuntimeError(f"ac_optim_workspace_floats failed: {lib.last_error()}")
+    ws = run.workspace("ac_optim_workspace_floats", host.data_ptr(), n, ng)   # lays the chunks out in the host table
     # pinned memory, copied on the current stream: torch's host allocator orders the reuse of `host` after the copy
-    d_tab = host.to(dev, non_blocking=True)
-    ws = torch.empty(wsf, dtype=torch.float32, device=dev)
-    norms = torch.empty(ng, dtype=torch.float32, device=dev)
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    _call("ac_optim_grad_norms", lib.ac_optim_grad_norms(dev.index, stream, host.data_ptr(), d_tab.data_ptr(), n, ng, ws.data_ptr(), norms.data_ptr()), lib)
-    _call("ac_optim_clip_adam_step", lib.ac_optim_clip_adam_step(dev.index, stream, host.data_ptr(), d_tab.data_ptr(), n, ng, norms.data_ptr(),
-                                                                 float(max_grad_norm), int(bool(clip))), lib)
+    d_tab = host.to(run.dev, non_blocking=True)
+    norms = run.empty(ng)
+    run("ac_optim_grad_norms", host, d_tab, n, ng, ws, norms)
+    run("ac_optim_clip_adam_step", host, d_tab, n, ng, norms, float(max_grad_norm), int(bool(clip)))
     return norms
 
 
