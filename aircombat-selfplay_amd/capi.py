@@ -223,6 +223,12 @@ class AcMiGather(C.Structure):
 AC_PPO_STAT_LOSS, AC_PPO_STAT_POLICY_LOSS, AC_PPO_STAT_VALUE_LOSS, AC_PPO_STAT_ENTROPY_LOSS, AC_PPO_STAT_RATIO_MEAN, AC_PPO_STAT_DENOMINATOR = range(6)
 AC_PPO_NSTAT = 8
 
+# ac_probe_math (include/aircombat.h): row widths and the ops in enum order
+AC_PROBE_IN, AC_PROBE_OUT, AC_PROBE_MAX_ROWS = 6, 12, 1 << 22
+AC_PROBE_OPS = ("fx_rcp", "fx_rsqrt", "fx_sqrt", "fx_sqrt_both", "fx_sincos", "atan2_fast", "acos_fast", "pow_pos", "tanh_fast", "atanh_fast",
+                "sigmoid_f", "tanh_f", "atmosphere", "pitot", "vcas", "in_range_deg", "in_range_rad", "slew", "tef_kinematic", "seek",
+                "posture_fn", "missile_height_f", "missile_height_d", "neu_height64", "locate", "locate_fast")
+
 # every symbol include/aircombat.h declares: (restype, argtypes)
 _p = C.c_void_p
 SIGNATURES = {
@@ -269,6 +275,7 @@ SIGNATURES = {
     "ac_controller_precision": (C.c_int, [_p]),
     "ac_controller_forward": (C.c_int, [C.c_int32, C.c_int32, _p, C.c_int64, C.c_int64, _p, _p, _p, _p]),
     "ac_selftest_missile_walk": (C.c_int, [C.c_int32, _p]),
+    "ac_probe_math": (C.c_int, [_p, C.c_int32, C.c_int64, _p, _p]),
     "ac_get_controller_state": (C.c_int, [_p, C.c_int32, C.c_int32, _p, _p]),
     "ac_set_controller_state": (C.c_int, [_p, C.c_int32, C.c_int32, _p]),
     "ac_snapshot_bytes": (C.c_int, [_p, C.POINTER(C.c_int64)]),

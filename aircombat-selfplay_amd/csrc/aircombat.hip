@@ -381,10 +381,12 @@ __device__ __forceinline__ void make_props(const State& s, const Derived& d, con
 
 // utils.py:58-103. v = (vN, vE, vDOWN) against an (N, E, UP) position, exactly as the reference mixes them.
 struct Geo { float AO, TA, R, side, cAO, cTA; };   // (cAO / cTA: the clipped cosines the angles were taken from)
-// acos for an argument already clipped to [-1, 1]: atan2(sqrt((1 - x)(1 + x)), x) on the polynomial atan2 (8e-8 rad); the product
-// form keeps the sine exact to an ulp where the angle is ill-conditioned (x -> +-1)
+// acos for an argument already clipped to [-1, 1]: atan2(sqrt((1 - x)(1 + x)), x) on the polynomial atan2: 1.8e-7 rad for x >= 0 and
+// 3.1e-7 rad for x < 0 with every fp32 operation correctly rounded (atan2_fast's figures for x > 0 and for all quadrants), 1.2e-7 more
+// for the ulps of v_sqrt_f32 and v_rcp_f32; the product form keeps the sine exact to an ulp where the angle is ill-conditioned (x -> +-1)
 __device__ __forceinline__ float acos_fast(float x) { return f16::atan2_fast(sqrtf((1.0f - x) * (1.0f + x)), x); }
-// tanh on the transcendental unit (|error| < 1e-6 absolute), atanh for x in (-1, 1)
+// tanh on the transcendental unit (|error| < 1e-6 absolute: 1.3e-7 with v_exp_f32 and the divide correctly rounded, 1.8e-7 more for their
+// ulps), atanh for x in (-1, 1)
 __device__ __forceinline__ float tanh_fast(float x) {
   const float t = __expf(2.0f * clampf(-10.0f, x, 10.0f));
   return (t - 1.0f) / (t + 1.0f);
@@ -462,7 +464,8 @@ __device__ __forceinline__ MslParam aim9l() {  // simulatior.py:421-433
   return MslParam{9.81f, 60.0f, 3.0f, 120.0f, 2.87f, 0.127f, 0.4f, 84.0f, 6.0f, 3.0f, 30.0f, 300.0f, 150.0f, 300, kb, kt};
 }
 // geodetic height of an NEU point (utils.py:44-55 -> pymap3d.ned2geodetic): ENU -> ECEF offset in fp64, then the
-// closed-form height of Fukushima's reduction (sub-millimetre, like pymap3d's You-2000 form)
+// closed-form height of Fukushima's reduction (sub-millimetre, like pymap3d's You-2000 form: 2.3e-9 m of fp64 rounding against the exact
+// ellipsoidal height over the +-60 km box, 0 to 20 km up)
 __device__ __forceinline__ double neu_height64(double n, double e, double u, const DevCfg& c) {
   double t = c.cLat0 * u - c.sLat0 * n;
   double dz = c.sLat0 * u + c.cLat0 * n;
@@ -482,9 +485,11 @@ __device__ __forceinline__ double neu_height64(double n, double e, double u, con
 }
 __device__ __forceinline__ float neu_height(float n, float e, float u, const DevCfg& c) { return (float)neu_height64(n, e, u, c); }
 // A missile only uses its geodetic height for the air density 1.225 exp(-h / 9300): the local-curvature form
-// h0 + u + n^2 / 2(M0 + h) + e^2 / 2(N0 + h) is within 4 cm of the exact reduction over +-60 km of the battle-field centre (3.5 mm
-// within 40 km), i.e. a density error below 5e-6 -- smaller than what the fp32 flight model's centimetres of target position do to
-// an intercept -- and costs a handful of operations instead of ~160 fp64 ones with four square roots (neu_height64 above).
+// h0 + u + n^2 / 2(M0 + h) + e^2 / 2(N0 + h) is within 4.1 cm of the exact reduction over the +-60 km box about the battle-field centre
+// (60 N: 40.2 mm at the box's corners at ground level, 39.8 mm there at 20 km; 9.5 mm over the +-40 km box; 13.9 mm within a 60 km
+// radius, 3.5 mm within a 40 km radius), i.e. a density error below 5e-6 -- smaller than what the fp32 flight model's centimetres of
+// target position do to an intercept -- and costs a handful of operations instead of ~160 fp64 ones with four square roots
+// (neu_height64 above).
 __device__ __forceinline__ float missile_height(float n, float e, float u, const DevCfg& c) {
   return c.h0 + u + n * n / (2.0f * (c.rm0 + u)) + e * e / (2.0f * (c.rn0 + u));
 }
@@ -2873,3 +2878,4 @@ int ac_get_missile_target(ac_env_t* h, int32_t env, int32_t agent, int32_t k, in
 #include "league_collect.hpp"
 #include "gru_layer_train.hpp"
 #include "mutual_support.hpp"
+#include "math_probe.hpp"

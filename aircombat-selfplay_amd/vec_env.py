@@ -25,6 +25,7 @@ import numpy as np
 
 from .capi import (AcConfig, AC_STATE_LEN, AC_TASK_HEADING, AC_TASK_SINGLECOMBAT, AC_TASK_SHOOT_MISSILE, AC_TASK_MULTICOMBAT, AC_TASK_SCENARIO1,
                    AC_TASK_SCENARIO_NVN, AC_CTL_FAST, AC_CTL_FP32, load_library)
+from . import capi
 from .config import config_from_yaml, default_config
 from .snapshot import EnvSnapshot, MultiSnapshot, SnapshotMismatch, check_compatible, decode_header
 
@@ -602,6 +603,18 @@ class HipVecEnv:
         out = C.c_uint64()
         self.lib.check(self.lib.ac_state_checksum(self._h, C.byref(out)), "ac_state_checksum")
         return int(out.value)
+
+    def probe_math(self, op, rows):
+        """Run device math primitive ``op`` (a name of capi.AC_PROBE_OPS or its index) on the rows of ``rows`` [n][<= 6] in one launch of
+        the probe kernel (ac_probe_math, include/aircombat.h) and return its results, float64 [n][12]. fp32 primitives read float32(rows)."""
+        op = capi.AC_PROBE_OPS.index(op) if isinstance(op, str) else int(op)
+        rows = np.asarray(rows, dtype=np.float64)
+        rows = rows.reshape(-1, 1) if rows.ndim == 1 else rows
+        src = np.zeros((rows.shape[0], capi.AC_PROBE_IN), dtype=np.float64)
+        src[:, :rows.shape[1]] = rows
+        out = np.empty((rows.shape[0], capi.AC_PROBE_OUT), dtype=np.float64)
+        self.lib.check(self.lib.ac_probe_math(self._h, op, src.shape[0], src.ctypes.data, out.ctypes.data), "ac_probe_math")
+        return out
 
     def full_state_checksum(self):
         """64-bit digest of every array a snapshot holds (ac_snapshot_checksum): the aircraft record, munitions, scenario and heading

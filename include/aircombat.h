@@ -227,6 +227,43 @@ int ac_split_bf16x3(const float* x, int64_t n, float* b0, float* b1, float* b2);
  * shared remembered missile (missile_posture_reward.py:18-46) against the round-by-round walk, for every combination of agent states
  * of a 2v2 and a 4v4 env. *mismatches receives the number of combinations that differ (0 = the two agree everywhere). */
 int ac_selftest_missile_walk(int32_t device_id, int32_t* mismatches);
+/* Test access to the device math primitives (needs the GPU): runs primitive `op` on n rows of arguments in one launch of a kernel that
+ * calls the inline functions the step kernels call. in [n][AC_PROBE_IN], out [n][AC_PROBE_OUT], host memory, row-major; arguments are
+ * read from the front of a row in the order listed below, results are written from the front of a row and the rest is zero. fp32
+ * primitives take (float)in[k] (pass float32-exact values) and their results are widened exactly. The handle supplies the battle-field
+ * constants (centre, radii of curvature) that missile_height and neu_height64 read; no env state is read or changed. Synchronous.
+ * Refused: a null handle or pointer, an op outside [0, AC_PROBE_NOPS), n <= 0 or n > AC_PROBE_MAX_ROWS. */
+enum { AC_PROBE_IN = 6, AC_PROBE_OUT = 12, AC_PROBE_MAX_ROWS = 1 << 22 };
+enum {
+  AC_PROBE_FX_RCP = 0,        /* (x)                           -> fx::rcp */
+  AC_PROBE_FX_RSQRT,          /* (x)                           -> fx::rsqrt */
+  AC_PROBE_FX_SQRT,           /* (x)                           -> fx::sqrt */
+  AC_PROBE_FX_SQRT_BOTH,      /* (x)                           -> sqrt, 1 / sqrt */
+  AC_PROBE_FX_SINCOS,         /* (x)                           -> sin, cos */
+  AC_PROBE_ATAN2_FAST,        /* (y, x)                        -> f16::atan2_fast */
+  AC_PROBE_ACOS_FAST,         /* (x)                           -> acos_fast */
+  AC_PROBE_POW_POS,           /* (x, y)                        -> f16::pow_pos */
+  AC_PROBE_TANH_FAST,         /* (x)                           -> tanh_fast */
+  AC_PROBE_ATANH_FAST,        /* (x)                           -> atanh_fast */
+  AC_PROBE_SIGMOID_F,         /* (x)                           -> ctl::sigmoid_f */
+  AC_PROBE_TANH_F,            /* (x)                           -> ctl::tanh_f */
+  AC_PROBE_ATMOSPHERE,        /* (h_ft)                        -> T [R], P [psf], rho [slug/ft3], a [ft/s] */
+  AC_PROBE_PITOT,             /* (mach, p)                     -> f16::pitot_impact_pressure */
+  AC_PROBE_VCAS,              /* (qc)                          -> f16::vcas_from_impact_pressure [ft/s] */
+  AC_PROBE_IN_RANGE_DEG,      /* (a)                           -> in_range_deg_f */
+  AC_PROBE_IN_RANGE_RAD,      /* (a)                           -> ctl::in_range_rad_f */
+  AC_PROBE_SLEW,              /* (out, in, lo, hi, rate)       -> f16::slew */
+  AC_PROBE_TEF_KINEMATIC,     /* (out, in)                     -> f16::tef_kinematic */
+  AC_PROBE_SEEK,              /* (v, target, accel, decel, dt) -> f16::seek */
+  AC_PROBE_POSTURE_FN,        /* (AO, TA, R km)                -> posture_fn */
+  AC_PROBE_MISSILE_HEIGHT_F,  /* (n, e, u) [m]                 -> missile_height, fp32 form */
+  AC_PROBE_MISSILE_HEIGHT_D,  /* (n, e, u) [m]                 -> missile_height, fp64 form */
+  AC_PROBE_NEU_HEIGHT64,      /* (n, e, u) [m]                 -> neu_height64 */
+  AC_PROBE_LOCATE,            /* (rx, ry, rz [ft, ECI], ticks) -> h_sl_ft, n_eci[3], e_eci[3], d_eci[3]  (f16::locate) */
+  AC_PROBE_LOCATE_FAST,       /* the same from f16::locate_fast (ticks is not read) */
+  AC_PROBE_NOPS
+};
+int ac_probe_math(ac_env_t* h, int32_t op, int64_t n, const double* in, double* out);
 
 /* timing helper for the bench: average device milliseconds per step kernel over the last n ac_step* calls, measured
  * with HIP events on the handle's stream */
