@@ -228,6 +228,9 @@ AC_PROBE_IN, AC_PROBE_OUT, AC_PROBE_MAX_ROWS = 6, 12, 1 << 22
 AC_PROBE_OPS = ("fx_rcp", "fx_rsqrt", "fx_sqrt", "fx_sqrt_both", "fx_sincos", "atan2_fast", "acos_fast", "pow_pos", "tanh_fast", "atanh_fast",
                 "sigmoid_f", "tanh_f", "atmosphere", "pitot", "vcas", "in_range_deg", "in_range_rad", "slew", "tef_kinematic", "seek",
                 "posture_fn", "missile_height_f", "missile_height_d", "neu_height64", "locate", "locate_fast")
+# ac_probe_missile (include/aircombat.h): row widths and limits
+AC_PROBE_MSL_IN, AC_PROBE_MSL_TGT, AC_PROBE_MSL_OUT = 16, 7, 16
+AC_PROBE_MSL_MAX_ROWS, AC_PROBE_MSL_MAX_TICKS, AC_PROBE_MSL_MAX_CELLS = 512, 4200, 1 << 19
 
 # every symbol include/aircombat.h declares: (restype, argtypes)
 _p = C.c_void_p
@@ -276,6 +279,7 @@ SIGNATURES = {
     "ac_controller_forward": (C.c_int, [C.c_int32, C.c_int32, _p, C.c_int64, C.c_int64, _p, _p, _p, _p]),
     "ac_selftest_missile_walk": (C.c_int, [C.c_int32, _p]),
     "ac_probe_math": (C.c_int, [_p, C.c_int32, C.c_int64, _p, _p]),
+    "ac_probe_missile": (C.c_int, [_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _p, _p, _p]),
     "ac_get_controller_state": (C.c_int, [_p, C.c_int32, C.c_int32, _p, _p]),
     "ac_set_controller_state": (C.c_int, [_p, C.c_int32, C.c_int32, _p]),
     "ac_snapshot_bytes": (C.c_int, [_p, C.POINTER(C.c_int64)]),

@@ -458,10 +458,12 @@ constexpr int first_tick_above(double limit) {       // smallest k with t_k > li
 // Overload only counts after "simulation/sim-time-sec > 10" (overload.py:30): JSBSim's clock is the fp64 running sum of dT
 // (FGFDMExec.cpp:196-203), and 600 additions of 1/60 already exceed 10, so the rule switches on at tick 600, not 601.
 constexpr int kTickOverload = first_tick_above(10.0);
-struct MslParam { float g, t_max, t_thrust, Isp, Length, Diameter, cD, m0, dm, K, nyz_max, Rc, v_min; int recede_max, k_burnout, k_timeout; };
+// (g and t_max are doubles: the fp64 overload takes its turn rates from g and its gain from t_max, and 9.81f / 27.22f are 4e-8 / 2.5e-8 off;
+//  cast to float they are the constants the fp32 code always had)
+struct MslParam { double g, t_max; float t_thrust, Isp, Length, Diameter, cD, m0, dm, K, nyz_max, Rc, v_min; int recede_max, k_burnout, k_timeout; };
 __device__ __forceinline__ MslParam aim9l() {  // simulatior.py:421-433
   constexpr int kb = first_tick_not_below(3.0), kt = first_tick_above(60.0);
-  return MslParam{9.81f, 60.0f, 3.0f, 120.0f, 2.87f, 0.127f, 0.4f, 84.0f, 6.0f, 3.0f, 30.0f, 300.0f, 150.0f, 300, kb, kt};
+  return MslParam{9.81, 60.0, 3.0f, 120.0f, 2.87f, 0.127f, 0.4f, 84.0f, 6.0f, 3.0f, 30.0f, 300.0f, 150.0f, 300, kb, kt};
 }
 // geodetic height of an NEU point (utils.py:44-55 -> pymap3d.ned2geodetic): ENU -> ECEF offset in fp64, then the
 // closed-form height of Fukushima's reduction (sub-millimetre, like pymap3d's You-2000 form: 2.3e-9 m of fp64 rounding against the exact
@@ -558,7 +560,9 @@ __device__ __forceinline__ void missile_run(MslT<R>& m, const MslParam& P, R tx,
 // fp64 munitions of the scenario tasks: the same update, still entirely in fp64, without the three fp64 sincos calls (~200
 // instructions each). After its first update a missile's velocity IS (v cos(theta) cos(psi), v cos(theta) sin(psi), v sin(theta)),
 // so sin / cos of the current angles are ratios of the velocity components, and the angles after the update follow by the
-// angle-addition formulas with the per-tick increment (|d| <= 0.03 rad: degree-9 Taylor terms are below 1e-18). Only the first
+// angle-addition formulas with the per-tick increment (|d| <= 0.05 rad: the terms left out are below 2e-18; a larger increment, which a
+// saturated demand near a vertical pitch gives, evaluates the functions of the new angles). The stored pitch is not confined to
+// [-pi/2, pi/2]: past it the ratios take the sign of its cosine (below). Only the first
 // tick after launch, whose velocity was inherited from the aircraft (with its down-for-up z component) while theta / psi came
 // from the aircraft attitude, evaluates the trigonometric functions.
 __device__ __forceinline__ void small_sincos(double d, double* s, double* c) {
@@ -624,7 +628,7 @@ __device__ __forceinline__ bool missile_run(MslD& m, const MslParam& P, double t
   } else {
     m.px += dt * m.vx; m.py += dt * m.vy; m.pz += dt * m.vz;
     // ---- drag and dv/dt (simulatior.py:578-590), fp32
-    const float gf = P.g, fvm = (float)vm;
+    const float gf = (float)P.g, fvm = (float)vm;
     const float alt = missile_height((float)m.px, (float)m.py, (float)m.pz, c);
     const float Tt = burning ? gf * P.Isp * P.dm : 0.0f;
     const float sd = sin_rate((float)m.dth), sp = sin_rate((float)m.dph);
@@ -634,7 +638,13 @@ __device__ __forceinline__ bool missile_run(MslD& m, const MslParam& P, double t
     const float nx = (Tt - D) / ((float)m.m * gf);
     double st, ct, sps, cps;   // of the CURRENT theta, psi
     if (k == 1) { fx::sincos(m.theta, &st, &ct); fx::sincos(m.psi, &sps, &cps); }
-    else { st = m.vz * ivm; ct = cth; cps = m.vx * ih; sps = m.vy * ih; }
+    else {
+      // The reference integrates the STORED pitch (simulatior.py:593-599), which a hard pull-up carries past +-pi/2; there its cosine is
+      // negative while hxy / v is the absolute value, and the heading the velocity shows is the stored one plus pi. The sign is the
+      // parity of the nearest multiple of pi.
+      const double sg = ((long long)rint(m.theta * 0.31830988618379067154) & 1) ? -1.0 : 1.0;
+      st = m.vz * ivm; ct = sg * cth; cps = sg * (m.vx * ih); sps = sg * (m.vy * ih);
+    }
     const float dv = gf * (nx - (float)st);
     m.dph = g * ivm * (ny * fx::rcp(ct));
     m.dth = g * ivm * (nz - ct);
@@ -642,7 +652,7 @@ __device__ __forceinline__ bool missile_run(MslD& m, const MslParam& P, double t
     const double dps = dt * m.dph, dts = dt * m.dth;
     m.psi += dps; m.theta += dts;
     double s2, c2, s3, c3;
-    if (fabs(dps) > 0.05 || fabs(dts) > 0.05) { fx::sincos(m.theta, &s2, &c2); fx::sincos(m.psi, &s3, &c3); }   // (never in the guidance envelope)
+    if (fabs(dps) > 0.05 || fabs(dts) > 0.05) { fx::sincos(m.theta, &s2, &c2); fx::sincos(m.psi, &s3, &c3); }   // (a saturated demand at low speed or near a vertical pitch: 0.08-0.46 rad per tick occur)
     else {
       double sa, ca, sb, cb;
       small_sincos(dts, &sa, &ca); small_sincos(dps, &sb, &cb);
@@ -2879,3 +2889,4 @@ int ac_get_missile_target(ac_env_t* h, int32_t env, int32_t agent, int32_t k, in
 #include "gru_layer_train.hpp"
 #include "mutual_support.hpp"
 #include "math_probe.hpp"
+#include "missile_probe.hpp"

@@ -87,7 +87,7 @@ __device__ __forceinline__ Ext fresh_ext(int num) {
 
 __device__ __forceinline__ MslParam aim120b() {  // the set both AIM_9M and AIM_120B carry, simulatior.py:659-672,696-709
   constexpr int kb = first_tick_not_below(1.4), kt = first_tick_above(27.22);
-  return MslParam{9.81f, 27.22f, 1.4f, 1837.0f, 3.66f, 0.18f, 0.02f, 152.0f, 6.0f, 5.0f, 50.0f, 5.0f, 150.0f, 300, kb, kt};
+  return MslParam{9.81, 27.22, 1.4f, 1837.0f, 3.66f, 0.18f, 0.02f, 152.0f, 6.0f, 5.0f, 50.0f, 5.0f, 150.0f, 300, kb, kt};
 }
 // decoy draw keyed by what is tested (substep, missile = launcher + uid number, chaff = releaser + release index): the
 // reference uses the global unseeded np.random (env_base.py:153), so only statistical parity with it is possible; the tests'

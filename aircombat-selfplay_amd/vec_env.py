@@ -616,6 +616,21 @@ class HipVecEnv:
         self.lib.check(self.lib.ac_probe_math(self._h, op, src.shape[0], src.ctypes.data, out.ctypes.data), "ac_probe_math")
         return out
 
+    def probe_missile(self, form, model, launch, target):
+        """Run the step kernels' missile integrator (``form`` 0 = MslT<float>, 1 = the MslD overload; ``model`` 0 = AIM-9L, 1 = AIM-120B)
+        from the launch rows ``launch`` [n][<= 16] against the target table ``target`` [ticks][n][7], one lane per row, with this
+        handle's battle-field centre (ac_probe_missile, include/aircombat.h). Returns the munition record after every tick, float64
+        [ticks][n][16]: status, position, velocity, theta, psi, t, m, dtheta, dphi, dprev, recede, moved."""
+        launch = np.asarray(launch, dtype=np.float64)
+        tgt = np.ascontiguousarray(target, dtype=np.float64)
+        assert launch.ndim == 2 and tgt.ndim == 3 and tgt.shape[1:] == (launch.shape[0], capi.AC_PROBE_MSL_TGT), (launch.shape, tgt.shape)
+        src = np.zeros((launch.shape[0], capi.AC_PROBE_MSL_IN), dtype=np.float64)
+        src[:, :launch.shape[1]] = launch
+        out = np.empty((tgt.shape[0], src.shape[0], capi.AC_PROBE_MSL_OUT), dtype=np.float64)
+        self.lib.check(self.lib.ac_probe_missile(self._h, int(form), int(model), src.shape[0], tgt.shape[0], src.ctypes.data, tgt.ctypes.data,
+                                                 out.ctypes.data), "ac_probe_missile")
+        return out
+
     def full_state_checksum(self):
         """64-bit digest of every array a snapshot holds (ac_snapshot_checksum): the aircraft record, munitions, scenario and heading
         state, controller state and the last outputs. ``state_checksum`` covers the aircraft record only."""

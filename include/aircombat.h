@@ -264,6 +264,23 @@ enum {
   AC_PROBE_NOPS
 };
 int ac_probe_math(ac_env_t* h, int32_t op, int64_t n, const double* in, double* out);
+/* Test access to the device missile integrators (needs the GPU): one lane per row runs `ticks` consecutive calls of the step kernels' own
+ * missile_run -- form AC_PROBE_MSL_FP32 the MslT<float> template of the 1v1 missile tasks, AC_PROBE_MSL_FP64 the MslD overload of the
+ * scenario tasks -- with the AIM-9L or the AIM-120B parameter set and the handle's battle-field constants. The step kernels fly fp32 +
+ * AIM-9L, fp64 + AIM-120B and fp64 + AIM-9L; fp32 + AIM-120B is refused. Host memory, row-major doubles:
+ *   launch [n][AC_PROBE_MSL_IN]          px py pz [m NEU], vx vy vz [m/s], theta, psi, t, m, dtheta, dphi, dprev (inf at launch), recede,
+ *                                        status (0 launched), one unused
+ *   target [ticks][n][AC_PROBE_MSL_TGT]  position [m NEU], the velocity record as the target's pose holds it, alive (non-zero)
+ *   out    [ticks][n][AC_PROBE_MSL_OUT]  status, px py pz, vx vy vz, theta, psi, t, m, dtheta, dphi, dprev, recede, moved
+ * after every tick; `moved` is the fp64 overload's return value (1 / 0) and -1 for the fp32 form. As in the step kernels, a row that
+ * reports HIT on a live target sees the target dead in its later ticks, and finished missiles keep being run. No env state is read or
+ * changed. Synchronous. Refused before any device call: a null handle or pointer, an unknown form or model, n outside
+ * [1, AC_PROBE_MSL_MAX_ROWS], ticks outside [1, AC_PROBE_MSL_MAX_TICKS], n * ticks above AC_PROBE_MSL_MAX_CELLS. */
+enum { AC_PROBE_MSL_IN = 16, AC_PROBE_MSL_TGT = 7, AC_PROBE_MSL_OUT = 16, AC_PROBE_MSL_MAX_ROWS = 512, AC_PROBE_MSL_MAX_TICKS = 4200,
+       AC_PROBE_MSL_MAX_CELLS = 1 << 19 };
+enum { AC_PROBE_MSL_FP32 = 0, AC_PROBE_MSL_FP64 = 1 };
+enum { AC_PROBE_MSL_AIM9L = 0, AC_PROBE_MSL_AIM120B = 1 };
+int ac_probe_missile(ac_env_t* h, int32_t form, int32_t model, int32_t n, int32_t ticks, const double* launch, const double* target, double* out);
 
 /* timing helper for the bench: average device milliseconds per step kernel over the last n ac_step* calls, measured
  * with HIP events on the handle's stream */

@@ -139,6 +139,8 @@ def lib():
         L.or_env_heading_pose.argtypes = [C.c_void_p] + [C.c_double] * 11
         L.or_env_heading_get.argtypes = [C.c_void_p, dp]
         L.or_missile_raw_run.argtypes = [dp, C.c_int, dp, dp, C.c_int]
+        L.or_missile_raw_run_at.argtypes = [dp, C.c_int, dp, dp, C.c_int] + [C.c_double] * 3
+        L.or_missile_raw_flyout.argtypes = [dp, C.c_int, C.c_int, C.c_int, dp] + [C.c_double] * 3 + [dp]
         L.or_env_set_shoot4.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int)]
         L.or_env_task_step.argtypes = [C.c_void_p]
         L.or_env_run_projectiles.argtypes = [C.c_void_p, C.c_int]

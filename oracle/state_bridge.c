@@ -177,19 +177,41 @@ void or_env_heading_get(const OrEnv* e, double out[5]) {
   out[0] = e->ac[0].target_heading_deg; out[1] = e->ac[0].target_altitude_ft; out[2] = e->ac[0].target_velocities_u_mps;
   out[3] = e->ac[0].heading_check_time; out[4] = e->heading_turn_counts;
 }
-void or_missile_raw_run(double* st /* [20] */, int model, const double tp[3], const double tv[3], int alive) {
-  /* flat missile state for the fly-out golden test: status, pos3, vel3, theta, psi, t, m, dtheta, dphi, dist_prev, recede_count, alt */
+void or_missile_raw_run_at(double* st /* [20] */, int model, const double tp[3], const double tv[3], int alive, double lon0, double lat0,
+                           double alt0) {
+  /* flat missile state for the fly-out golden test: status, pos3, vel3, theta, psi, t, m, dtheta, dphi, dist_prev, recede_count, alt;
+     the battle-field centre is the caller's */
   OrMissile m;
   or_missile_init(&m, model, 1.0 / 60.0);
   m.status = (int)st[0];
   for (int k = 0; k < 3; k++) { m.position[k] = st[1 + k]; m.velocity[k] = st[4 + k]; }
   m.posture[1] = st[7]; m.posture[2] = st[8]; m.t = st[9]; m.m = st[10]; m.dtheta = st[11]; m.dphi = st[12]; m.dist_prev = st[13];
   m.recede_count = (int)st[14]; m.geodetic[2] = st[15];
-  or_missile_run(&m, tp, tv, alive, 1.0 / 60.0, 120.0, 60.0, 0.0);
+  or_missile_run(&m, tp, tv, alive, 1.0 / 60.0, lon0, lat0, alt0);
   st[0] = m.status;
   for (int k = 0; k < 3; k++) { st[1 + k] = m.position[k]; st[4 + k] = m.velocity[k]; }
   st[7] = m.posture[1]; st[8] = m.posture[2]; st[9] = m.t; st[10] = m.m; st[11] = m.dtheta; st[12] = m.dphi; st[13] = m.dist_prev;
   st[14] = m.recede_count; st[15] = m.geodetic[2];
+}
+void or_missile_raw_run(double* st /* [20] */, int model, const double tp[3], const double tv[3], int alive) {
+  or_missile_raw_run_at(st, model, tp, tv, alive, 120.0, 60.0, 0.0);
+}
+/* n independent fly-outs of `ticks` calls of or_missile_raw_run_at each: st [n][20] (left at the last tick's state), target
+   [ticks][n][7] = position, velocity record, alive; out [ticks][n][20] receives the flat state after every tick. A row whose missile
+   reports HIT on a live target sees that target dead from then on (simulatior.py:525-527), and a finished missile keeps being run
+   (env_base.py:142-143). */
+void or_missile_raw_flyout(double* st, int n, int ticks, int model, const double* target, double lon0, double lat0, double alt0, double* out) {
+  for (int r = 0; r < n; r++) {
+    double* s = st + 20 * (size_t)r;
+    int shot = 0;
+    for (int k = 0; k < ticks; k++) {
+      const double* t = target + 7 * ((size_t)k * n + r);
+      int alive = t[6] != 0.0 && !shot;
+      or_missile_raw_run_at(s, model, t, t + 3, alive, lon0, lat0, alt0);
+      if ((int)s[0] == OR_MSL_HIT && alive) shot = 1;
+      memcpy(out + 20 * ((size_t)k * n + r), s, 20 * sizeof(double));
+    }
+  }
 }
 
 /* ---- scenario-task golden hooks */
