@@ -220,6 +220,15 @@ class AcMiGather(C.Structure):
                [(n, C.c_void_p) for n in ("OBS", "ACTIONS", "RNN_ACTOR", "times", "X", "Y")]
 
 
+AC_LATE_FRACTION_DEFAULT, AC_LATE_BUDGET_DEFAULT = 1.0, 400000   # include/aircombat.h
+
+
+class AcLateStats(C.Structure):
+    """ac_late_stats_t (include/aircombat.h): what the host steps through ac_step_host_actions counted and, while timing is on, took."""
+    _fields_ = [("steps", C.c_int64), ("retries", C.c_int64), ("last_retries", C.c_int32), ("last_late", C.c_int32), ("retry_steps", C.c_int64), ("lowered", C.c_int64), ("disabled", C.c_int64), ("fraction", C.c_double), ("timed_steps", C.c_int64),
+                ("copy_before_us", C.c_double), ("dispatch_us", C.c_double), ("copy_after_us", C.c_double), ("wait_us", C.c_double)]
+
+
 AC_PPO_STAT_LOSS, AC_PPO_STAT_POLICY_LOSS, AC_PPO_STAT_VALUE_LOSS, AC_PPO_STAT_ENTROPY_LOSS, AC_PPO_STAT_RATIO_MEAN, AC_PPO_STAT_DENOMINATOR = range(6)
 AC_PPO_NSTAT = 8
 
@@ -250,6 +259,9 @@ SIGNATURES = {
     "ac_step_host_async": (C.c_int, [_p, C.c_int32]),
     "ac_step_host_wait": (C.c_int, [_p]),
     "ac_step_host": (C.c_int, [_p, C.c_int32]),
+    "ac_step_host_actions": (C.c_int, [_p, C.c_int32, _p, C.c_size_t]),
+    "ac_late_config": (C.c_int, [_p, C.c_double, C.c_int32, C.c_int32, C.c_int32]),
+    "ac_late_stats": (C.c_int, [_p, _p]),   # (AcLateStats by reference)
     "ac_order_after": (C.c_int, [_p, _p]),
     "ac_order_before": (C.c_int, [_p, _p]),
     "ac_step_async_device": (C.c_int, [_p, _p]),

@@ -866,8 +866,12 @@ struct TaskTraits {
 
 // FORM: 0 = one wave per 64 aircraft, 1 = the three-wave form (split_kernel.hpp) for the task without munitions at small grids,
 // 2 = the pair form (pair_kernel.hpp: flight wave + environment wave) for the tasks with missiles.
-template <int TASK, int WPE, int FORM = 0>
-__global__ __launch_bounds__(FORM == 1 ? 192 : (FORM == 2 ? 128 : (FORM == 3 ? 256 : 64)), WPE) void step_kernel_1v1(DevPtrs P, DevCfg c) {
+// LATE (three-wave SingleCombat, act_dim 4, launched only by ac_step_host_actions): the action rows may still be on their way into the
+// mapped set when the systems wave reads them; `ahdr` is the set's header block (LateActionFetch, split_kernel.hpp). Every other
+// instantiation never reads that argument.
+template <int TASK, int WPE, int FORM = 0, bool LATE = false>
+__global__ __launch_bounds__(FORM == 1 ? 192 : (FORM == 2 ? 128 : (FORM == 3 ? 256 : 64)), WPE) void step_kernel_1v1(DevPtrs P, DevCfg c, int* ahdr) {
+  static_assert(!LATE || FORM == 1, "late actions: the three-wave form only");
   // forms launch_step reaches: SingleCombat in the one-wave (0) and three-wave (1) forms; the two tasks with munitions in the pair (2) and quad (3) forms only
   static_assert(TASK == AC_TASK_SINGLECOMBAT ? FORM <= 1 : FORM >= 2, "no launch path for this (task, form)");
   using TT = TaskTraits<TASK>;
@@ -899,6 +903,7 @@ __global__ __launch_bounds__(FORM == 1 ? 192 : (FORM == 2 ? 128 : (FORM == 3 ? 2
   const float* act = P.actions + (size_t)nn * c.act_dim;
   float4 a4;
   ActionFetch arow;                      // three-wave / quad form: the systems wave's action row (asked for late, waited for by hand)
+  LateActionFetch lrow;                  // LATE: the same row, tagged and possibly not there yet
   float shoot_raw = 0.0f;
   if (SPLIT) {
     TableCopy<192> tc;
@@ -923,7 +928,10 @@ __global__ __launch_bounds__(FORM == 1 ? 192 : (FORM == 2 ? 128 : (FORM == 3 ? 2
     // left anywhere behind this point (the counter counts all loads: it would wait for the row as well) -- before the one it does not
     // know of is issued
     __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0): the wave's own state, one round trip like the tables
-    if (role == 1) arow.issue(act, c.act_dim);
+    if (role == 1) {
+      if constexpr (LATE) lrow.issue(act, ahdr, P.err);
+      else arow.issue(act, c.act_dim);
+    }
     AC_CLKW(0, 120); AC_CLKW(1, 121); AC_CLKW(2, 122);
     __syncthreads();                      // (LDS visibility; loads in flight are not waited for)
   } else if (QUAD) {
@@ -984,7 +992,10 @@ __global__ __launch_bounds__(FORM == 1 ? 192 : (FORM == 2 ? 128 : (FORM == 3 ? 2
   constexpr bool OBS_BY_KIN = SPLIT && TASK == AC_TASK_SINGLECOMBAT;
   if (SPLIT) {   // helper waves: run their part of every substep (the systems wave decodes the commands it integrates)
     const int role = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    if (split_helper_wave(s, t, T, L, l, c.substeps, nullptr, nullptr, &arow)) {
+    bool helper;
+    if constexpr (LATE) helper = split_helper_wave<false, false, LateActionFetch>(s, t, T, L, l, c.substeps, nullptr, nullptr, &lrow);
+    else helper = split_helper_wave(s, t, T, L, l, c.substeps, nullptr, nullptr, &arow);
+    if (helper) {
       if (OBS_BY_KIN && role == 1) {                 // the systems wave, idle after its last tick: the two geometry rewards of the final pose
         using namespace mail;
         wg_sync();                                   // the dynamics wave has posted the final pose
@@ -1714,6 +1725,7 @@ static uint64_t fnv1a(uint64_t hsh, const void* p, size_t n) {
   } while (0)
 
 #include "aql_dispatch.hpp"
+#include "late_actions.hpp"
 
 struct ac_recorder;
 struct ac_spawn;
@@ -1739,8 +1751,22 @@ struct ac_env {
   bool mark_mid;
   hipEvent_t ev_order;                   // stream-ordering hand-shake with the caller's streams (ac_order_after / ac_order_before)
   // ac_step_host: two library-owned sets of pinned host buffers mapped into the device (actions in; obs, rewards, dones, info out)
-  struct HostSet { float* act; float* obs; float* rew; uint8_t* done; int* info; } hs[AC_HOST_SETS];   // allocated on first use (ac_host_buffers)
+  struct HostSet {
+    float* act; float* obs; float* rew; uint8_t* done; int* info;
+    int* hdr;          // late actions: the set's header block (late_actions.hpp), in the same allocation behind the action rows
+    uint32_t tag;      // ... the tag of its last late use
+    bool plain_rows;   // ... and whether a plain step has put untagged rows there since (they could carry a tag's bits by accident)
+  } hs[AC_HOST_SETS];   // allocated on first use (ac_host_buffers)
   bool have_hs[AC_HOST_SETS];
+  // ac_step_host_actions: share of the batch copied behind the doorbell, a test's pause between doorbell and copy, and what the last
+  // such step and all of them together counted and (late_timing) took
+  double late_fraction;
+  int late_budget;
+  int late_delay_us;
+  bool late_timing;
+  bool late_off;         // the self-check below turned the late order off for this handle (ac_late_config turns it on again)
+  int late_win_steps, late_win_retry;   // ... its window: late steps, and those among them in which a wave had to ask again
+  ac_late_stats_t late_stats;
   int* err_host;                         // P.err: one word of page-locked host memory the step kernels write on a non-finite state (sticky until ac_reset)
   int err_sticky;
   int* count_host;                       // ac_munitions_in_flight's counter: one page-locked, device-mapped word allocated with the handle
@@ -1757,6 +1783,7 @@ struct ac_env {
   bool snap_hdr_ok;
   // host steps as AQL packets on a queue of the handle's own (aql_dispatch.hpp)
   AqlState aql;
+  int late_set;                          // the set of the late step in flight (its retry count is read after the wait), or -1
   bool stream_dirty;                     // work enqueued on `stream` since it was last synchronised: the next AQL dispatch synchronises it
   ac_recorder* rec;                      // the attached flight recorder (flight_recorder.hpp), captured behind every step and reset; null: none
   ac_spawn* spawn;                       // the attached spawn bank (spawn_bank.hpp), applied behind every step and reset, ahead of the recorder; null: none
@@ -1776,6 +1803,8 @@ static void geodetic2ecef_m(double lat_deg, double lon_deg, double alt, double* 
 static int check_nonfinite(ac_env* h, const char* who) {
   if (h->err_host && *(volatile int*)h->err_host) h->err_sticky = *(volatile int*)h->err_host;
   if (!h->err_sticky) return 0;
+  if (h->err_sticky == AC_ERR_LATE_ACTIONS)   // (split_kernel.hpp: a systems wave ran out of tries; below every non-finite code)
+    return fail(std::string(who) + ": the step's action rows did not reach the device within the retry budget; the step flew on stale actions (ac_reset clears the condition)");
   const int n = std::max(0, std::min(0x3fffffff - (h->err_sticky & 0x3fffffff), h->N - 1));   // emit_scalars: (own probe << 30) | (0x3fffffff - aircraft)
   char msg[192];
   snprintf(msg, sizeof msg, "%s: JSBSim failed. Non-finite state or reward in env %d, agent %d (ac_reset clears the condition)", who, n / h->A, n % h->A);
@@ -1790,13 +1819,18 @@ static int ctl_rows_pin() {
 }
 // The kernel(s) of one step, chosen from the handle's task, kernel form and grid, with their arguments packed as the kernarg segment holds
 // them. launch_step launches the plan through HIP; a host step on the AQL path dispatches the same plan (aql_dispatch.hpp).
-static int step_plan(ac_env* h, const float* d_actions, int host_set, StepPlan* sp) {
+static int step_plan(ac_env* h, const float* d_actions, int host_set, StepPlan* sp, bool want_late = false) {
   DevPtrs p = h->dp;
   p.actions = d_actions ? d_actions : h->d_actions;
   if (host_set >= 0) {   // actions read from, and a second copy of every output written to, mapped host memory
     const ac_env::HostSet& hs = h->hs[host_set];
     p.actions = hs.act; p.obs2 = hs.obs; p.rew2 = hs.rew; p.done2 = hs.done; p.info2 = hs.info;
   }
+  // the one kernel form with a twin that reads tagged rows (LateActionFetch, split_kernel.hpp), and only for a host set
+  int* ahdr = nullptr;
+  if (host_set >= 0 && h->cfg.task == AC_TASK_SINGLECOMBAT && h->split_waves && !h->cfg.hierarchical && h->act_dim == 4) ahdr = h->hs[host_set].hdr;
+  sp->late = want_late && ahdr != nullptr;
+  sp->twin = nullptr;
   sp->n = 0;
   const dim3 block(64), grid((h->N + 63) / 64);
   auto add = [&](const void* fn, dim3 g, dim3 b) -> KLaunch& {
@@ -1806,6 +1840,7 @@ static int step_plan(ac_env* h, const float* d_actions, int host_set, StepPlan* 
   };
   // the three argument lists of the step kernel families
   auto pd = [&](const void* fn, dim3 b) { KLaunch& k = add(fn, grid, b); k.arg(p); k.arg(h->dc); };
+  auto pd1 = [&](const void* fn, dim3 b) { KLaunch& k = add(fn, grid, b); k.arg(p); k.arg(h->dc); k.arg(ahdr); };   // step_kernel_1v1
   auto scen = [&](const void* fn, dim3 b) {
     KLaunch& k = add(fn, grid, b);
     k.arg(p); k.arg(h->dc); k.arg(h->d_XF); k.arg(h->d_XI); k.arg((const float*)nullptr); k.arg((const int*)nullptr);
@@ -1859,17 +1894,21 @@ static int step_plan(ac_env* h, const float* d_actions, int host_set, StepPlan* 
     else if (h->A == 4) pd(one_wave_per_simd ? AC_K(step_kernel_nvn<4, 1>) : AC_K(step_kernel_nvn<4, 2>), block);
     else pd(one_wave_per_simd ? AC_K(step_kernel_nvn<8, 1>) : AC_K(step_kernel_nvn<8, 2>), block);
   } else if (h->cfg.task == AC_TASK_SINGLECOMBAT) {
-    if (h->split_waves) pd(AC_K(step_kernel_1v1<AC_TASK_SINGLECOMBAT, 1, 1>), dim3(192));
-    else if (one_wave_per_simd) pd(AC_K(step_kernel_1v1<AC_TASK_SINGLECOMBAT, 1, 0>), block);
-    else pd(AC_K(step_kernel_1v1<AC_TASK_SINGLECOMBAT, 2, 0>), block);
+    if (h->split_waves) {   // (the two kernels take the same argument bytes: a host set's kernarg block serves both)
+      const void* plain = AC_K(step_kernel_1v1<AC_TASK_SINGLECOMBAT, 1, 1>);
+      const void* late = AC_K(step_kernel_1v1<AC_TASK_SINGLECOMBAT, 1, 1, true>);
+      pd1(sp->late ? late : plain, dim3(192));
+      if (ahdr) sp->twin = sp->late ? plain : late;
+    } else if (one_wave_per_simd) pd1(AC_K(step_kernel_1v1<AC_TASK_SINGLECOMBAT, 1, 0>), block);
+    else pd1(AC_K(step_kernel_1v1<AC_TASK_SINGLECOMBAT, 2, 0>), block);
   } else if (h->cfg.task == AC_TASK_DODGE_MISSILE) {
-    if (h->quad_waves) pd(AC_K(step_kernel_1v1<AC_TASK_DODGE_MISSILE, 1, 3>), dim3(256));
-    else if (pair_wpe1) pd(AC_K(step_kernel_1v1<AC_TASK_DODGE_MISSILE, 1, 2>), dim3(128));
-    else pd(AC_K(step_kernel_1v1<AC_TASK_DODGE_MISSILE, 2, 2>), dim3(128));
+    if (h->quad_waves) pd1(AC_K(step_kernel_1v1<AC_TASK_DODGE_MISSILE, 1, 3>), dim3(256));
+    else if (pair_wpe1) pd1(AC_K(step_kernel_1v1<AC_TASK_DODGE_MISSILE, 1, 2>), dim3(128));
+    else pd1(AC_K(step_kernel_1v1<AC_TASK_DODGE_MISSILE, 2, 2>), dim3(128));
   } else {
-    if (h->quad_waves) pd(AC_K(step_kernel_1v1<AC_TASK_SHOOT_MISSILE, 1, 3>), dim3(256));
-    else if (pair_wpe1) pd(AC_K(step_kernel_1v1<AC_TASK_SHOOT_MISSILE, 1, 2>), dim3(128));
-    else pd(AC_K(step_kernel_1v1<AC_TASK_SHOOT_MISSILE, 2, 2>), dim3(128));
+    if (h->quad_waves) pd1(AC_K(step_kernel_1v1<AC_TASK_SHOOT_MISSILE, 1, 3>), dim3(256));
+    else if (pair_wpe1) pd1(AC_K(step_kernel_1v1<AC_TASK_SHOOT_MISSILE, 1, 2>), dim3(128));
+    else pd1(AC_K(step_kernel_1v1<AC_TASK_SHOOT_MISSILE, 2, 2>), dim3(128));
   }
 #undef AC_K
   for (int i = 0; i < sp->n; ++i)
@@ -1921,13 +1960,61 @@ static int host_entry(ac_env* h) {
 // A host step: through the AQL queue once it is set up (and no timing bracket is open: bench.py times host steps with HIP events on the
 // stream), else through HIP; the first host step of a handle goes through HIP and sets the queue up after it. A handle with a flight
 // recorder or a spawn bank attached takes its host steps through HIP launches: their kernels are launches on the stream, behind the step's.
-static int host_step(ac_env* h, int set) {
+//
+// `src` (ac_step_host_actions): the caller's action batch, still to be copied into the set. Where the plan is the late-capable kernel and
+// the step goes through the AQL queue, the set's header word announces the step's tag, a share 1 - late_fraction of the rows is copied and
+// tagged in front of the doorbell and the rest behind it, under the launch (late_actions.hpp); anywhere else the batch is copied first,
+// untagged, and the header word says "plain rows" -- as it does for every step whose rows the caller put there itself.
+static int host_step(ac_env* h, int set, const float* src = nullptr) {
   if (aql_settle(h)) return -1;
   StepPlan sp;
-  if (step_plan(h, nullptr, set, &sp)) return -1;
   AqlState& a = h->aql;
-  bool aql = a.mode == AqlState::READY && !h->timing && !h->rec && !h->spawn && sp.n == a.nkern;
-  for (int i = 0; aql && i < sp.n; ++i) aql = sp.k[i].fn == a.kern[i].fn;
+  // the late kernel only where the step can go through the AQL queue and the handle's self-check has not turned the path off
+  const bool may_aql = a.mode == AqlState::READY && !h->timing && !h->rec && !h->spawn;
+  if (step_plan(h, nullptr, set, &sp, src && may_aql && !h->late_off)) return -1;
+  bool aql = may_aql && sp.n == a.nkern;
+  for (int i = 0; aql && i < sp.n; ++i) aql = aql_kern(&a, i, sp.k[i].fn) != nullptr;
+  ac_env::HostSet& hs = h->hs[set];
+  const bool late = aql && sp.late && sp.n == 1;
+  if (sp.late && !late) return fail("host_step: the late kernel was planned for a step that cannot be dispatched as an AQL packet");
+  if (src && !late) memcpy(hs.act, src, sizeof(float) * (size_t)h->N * h->act_dim);
+  if (hs.hdr && !late) { hs.hdr[late::HDR_TAG] = 0; hs.plain_rows = true; }
+  h->late_stats.last_late = late ? 1 : 0;
+  if (late) {
+    using clk = std::chrono::steady_clock;
+    const bool timed = h->late_timing;
+    clk::time_point t0, t1, t2, t3;
+    if (timed) t0 = clk::now();
+    if (stream_settle(h)) return -1;
+    const size_t rows = (size_t)h->N;
+    // rows a plain step left in the set could carry the tag's bits by accident: then the whole batch goes in front of the doorbell
+    const size_t nb = hs.plain_rows ? rows : late::rows_before(rows, h->late_fraction);
+    hs.tag = late::next_tag(hs.tag);
+    hs.plain_rows = false;
+    hs.hdr[late::HDR_RETRIES] = 0;
+    hs.hdr[late::HDR_BUDGET] = h->late_budget;
+    hs.hdr[late::HDR_TAG] = (int)hs.tag;
+    late::copy_tag_rows(hs.act, src, 0, nb, hs.tag);
+    if (timed) t1 = clk::now();
+    const std::string e = aql_dispatch(&a, sp, set);
+    if (!e.empty()) return aql_fault(h, e);
+    if (timed) t2 = clk::now();
+    if (h->late_delay_us > 0) {   // (tests: the only way the kernel's retry path runs at all)
+      const auto until = clk::now() + std::chrono::microseconds(h->late_delay_us);
+      while (clk::now() < until) {}
+    }
+    late::copy_tag_rows(hs.act, src, nb, rows, hs.tag);
+    if (timed) {
+      t3 = clk::now();
+      ac_late_stats_t& st = h->late_stats;
+      st.timed_steps += 1;
+      st.copy_before_us += std::chrono::duration<double, std::micro>(t1 - t0).count();
+      st.dispatch_us += std::chrono::duration<double, std::micro>(t2 - t1).count();
+      st.copy_after_us += std::chrono::duration<double, std::micro>(t3 - t2).count();
+    }
+    h->late_set = set;
+    return 0;
+  }
   if (aql) {
     if (stream_settle(h)) return -1;
     const std::string e = aql_dispatch(&a, sp, set);
@@ -2109,6 +2196,8 @@ int ac_create(const ac_config_t* cfg, int32_t n_envs, int32_t device_id, uint64_
   c.obs_dim = h->obs_dim; c.act_dim = h->act_low; c.N = h->N;
   c.msl_slots = scenario ? 2 : ((cfg->task == AC_TASK_SHOOT_MISSILE || cfg->task == AC_TASK_DODGE_MISSILE) ? AC_MAX_MISSILES_PER_AGENT : 0);
   c.chaff_seed = seed;
+  h->late_budget = AC_LATE_BUDGET_DEFAULT;
+  h->late_fraction = AC_LATE_FRACTION_DEFAULT;
   c.rwr = cfg->rwr ? 1 : 0;
   c.tobs = tmpl_obs;
   c.legacy_obs = (((cfg->task == AC_TASK_SCENARIO_NVN || cfg->task == AC_TASK_MULTICOMBAT) && cfg->legacy_obs) || nvn_dodge) ? 1 : 0;
@@ -2294,7 +2383,11 @@ int ac_host_buffers(ac_env_t* h, int32_t set, float** actions, float** obs, floa
     const size_t Npad = ((size_t)h->N + 63) / 64 * 64;
     // hipHostMallocDefault: page-locked, mapped into the device's address space, coherent (kernel stores are visible to the host
     // once the kernel has completed)
-    HIP_OK(hipHostMalloc((void**)&hs.act, sizeof(float) * Npad * h->act_dim, hipHostMallocDefault));
+    const size_t act_bytes = (sizeof(float) * Npad * h->act_dim + 63) / 64 * 64;   // (the header block sits on a line of its own behind the rows)
+    HIP_OK(hipHostMalloc((void**)&hs.act, act_bytes + sizeof(int) * late::HDR_WORDS, hipHostMallocDefault));
+    hs.hdr = reinterpret_cast<int*>(reinterpret_cast<char*>(hs.act) + act_bytes);
+    memset(hs.hdr, 0, sizeof(int) * late::HDR_WORDS);
+    hs.tag = 0; hs.plain_rows = false;
     HIP_OK(hipHostMalloc((void**)&hs.obs, sizeof(float) * Npad * h->obs_dim, hipHostMallocDefault));
     HIP_OK(hipHostMalloc((void**)&hs.rew, sizeof(float) * Npad, hipHostMallocDefault));
     HIP_OK(hipHostMalloc((void**)&hs.done, Npad, hipHostMallocDefault));
@@ -2345,6 +2438,61 @@ int ac_step_host_wait(ac_env_t* h) {
 int ac_step_host(ac_env_t* h, int32_t set) {   // step_async + step_wait in one call (VecEnv.step, env_wrappers.py:30-42)
   if (ac_step_host_async(h, set)) return -1;
   return ac_step_host_wait(h);
+}
+// The same from the caller's own array: header word, doorbell, copy, wait (host_step). What the step kernel's retry counter holds after
+// the wait goes into the handle's statistics.
+int ac_step_host_actions(ac_env_t* h, int32_t set, const float* actions, size_t n_floats) {
+  if (!h || !actions || set < 0 || set >= AC_HOST_SETS) return fail("ac_step_host_actions: bad argument");
+  if (!h->have_hs[set]) return fail("ac_step_host_actions: call ac_host_buffers for this set first");
+  if (n_floats != (size_t)h->N * h->act_dim) return fail("ac_step_host_actions: n_floats is not num_envs * num_agents * act_dim");
+  HIP_OK(hipSetDevice(h->device));
+  h->late_set = -1;
+  if (host_step(h, set, actions)) return -1;
+  const int ls = h->late_set;
+  std::chrono::steady_clock::time_point t0;
+  if (ls >= 0 && h->late_timing) t0 = std::chrono::steady_clock::now();
+  const int rc = ac_step_host_wait(h);
+  if (ls >= 0) {
+    ac_late_stats_t& st = h->late_stats;
+    if (h->late_timing) st.wait_us += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
+    st.last_retries = *(volatile int*)&h->hs[ls].hdr[late::HDR_RETRIES];
+    st.retries += st.last_retries;
+    st.retry_steps += st.last_retries != 0;
+    st.steps += 1;
+    // Self-check: a host thread held up behind the doorbell makes a handful of steps in thousands retry (profiles/late_actions_summary.txt:
+    // at most 3 in 2000). Where the copy does not fit under the launch -- a slower copy (cold source arrays), a faster dispatch -- steps
+    // retry as a rule, at ~1.6 us a try: more than AC_LATE_WINDOW_MAX_RETRY_STEPS of AC_LATE_WINDOW steps move a quarter of the batch back
+    // in front of the doorbell, and with nothing left behind it the handle goes back to copy-first and the plain kernel.
+    h->late_win_steps += 1;
+    h->late_win_retry += st.last_retries != 0;
+    if (h->late_win_steps == AC_LATE_WINDOW) {
+      if (h->late_win_retry > AC_LATE_WINDOW_MAX_RETRY_STEPS) {
+        h->late_fraction -= 0.25;
+        st.lowered += 1;
+        if (h->late_fraction <= 0.0) { h->late_fraction = 0.0; h->late_off = true; st.disabled = 1; }
+      }
+      h->late_win_steps = h->late_win_retry = 0;
+    }
+    st.fraction = h->late_fraction;
+    h->late_set = -1;
+  }
+  return rc;
+}
+int ac_late_config(ac_env_t* h, double fraction, int32_t budget, int32_t delay_us, int32_t timing) {
+  if (!h) return fail("ac_late_config: null handle");
+  if (fraction > 1.0 || budget > (1 << 24)) return fail("ac_late_config: fraction above 1 or budget above 2^24 tries");
+  if (host_entry(h)) return -1;
+  if (fraction >= 0.0) { h->late_fraction = fraction; h->late_off = false; h->late_stats.disabled = 0; h->late_win_steps = h->late_win_retry = 0; }
+  if (budget >= 0) h->late_budget = budget;
+  if (delay_us >= 0) h->late_delay_us = delay_us;
+  if (timing >= 0) h->late_timing = timing != 0;
+  return 0;
+}
+int ac_late_stats(ac_env_t* h, ac_late_stats_t* out) {
+  if (!h || !out) return fail("ac_late_stats: null argument");
+  *out = h->late_stats;
+  out->fraction = h->late_fraction;
+  return 0;
 }
 
 // ---- stream ordering for the device-resident path: the handle's stream is non-blocking, so work on the caller's streams (a torch

@@ -40,6 +40,8 @@ struct KLaunch {
 struct StepPlan {
   KLaunch k[2];      // hierarchical handles: controller kernel, then the step kernel; else the step kernel alone
   int n = 0;
+  bool late = false;          // the step kernel is the one that reads tagged rows: they may be copied behind the doorbell (late_actions.hpp)
+  const void* twin = nullptr; // the other kernel of that pair (plain <-> late), which takes the same argument bytes; null: there is none
 };
 
 struct AqlState {   // (plain bytes: ac_create zeroes the handle, which is the PENDING state)
@@ -55,12 +57,19 @@ struct AqlState {   // (plain bytes: ac_create zeroes the handle, which is the P
   volatile int qerr = HSA_STATUS_SUCCESS;  // written by the queue's error callback
   struct Kern { const void* fn; uint64_t object; uint32_t group, priv, kernarg; } kern[2]{};
   int nkern = 0;
+  Kern twin{};                           // the plan's twin of the step kernel (StepPlan::twin), dispatched in its place when the plan names it
   unsigned char* d_args = nullptr;       // [AC_HOST_SETS][2][KLaunch::kCap] in device memory
   unsigned char cached[AC_HOST_SETS][2][KLaunch::kCap];   // what each block holds
   bool have_block[AC_HOST_SETS]{};
   bool in_flight = false;
 };
 
+// the resolved kernel behind entry i of a plan: the one the queue was set up with, or its twin
+static const AqlState::Kern* aql_kern(const AqlState* a, int i, const void* fn) {
+  if (a->kern[i].fn == fn) return &a->kern[i];
+  if (i == a->nkern - 1 && a->twin.fn && a->twin.fn == fn) return &a->twin;
+  return nullptr;
+}
 static void aql_queue_error(hsa_status_t s, hsa_queue_t*, void* data) { ((AqlState*)data)->qerr = (int)s; }
 
 static std::string hsa_msg(const char* what, hsa_status_t s) {
@@ -124,19 +133,23 @@ static std::string aql_setup(AqlState* a, int device, const StepPlan& plan) {
   s = hsa_system_get_major_extension_table(HSA_EXTENSION_AMD_LOADER, 1, sizeof loader, &loader);
   if (s != HSA_STATUS_SUCCESS) return hsa_msg("AMD loader extension", s);
   a->nkern = plan.n;
-  for (int i = 0; i < plan.n; ++i) {
-    const char* name = hipKernelNameRefByPtr(plan.k[i].fn, nullptr);
+  a->twin = AqlState::Kern{};
+  for (int i = 0; i < plan.n + (plan.twin ? 1 : 0); ++i) {
+    const bool tw = i == plan.n;           // (the twin takes the last kernel's arguments)
+    const void* fn = tw ? plan.twin : plan.k[i].fn;
+    const char* name = hipKernelNameRefByPtr(fn, nullptr);
     if (!name) return "hipKernelNameRefByPtr found no name for a step kernel";
-    AqlState::Kern& k = a->kern[i];
-    k.fn = plan.k[i].fn;
+    AqlState::Kern& k = tw ? a->twin : a->kern[i];
+    k.fn = fn;
     AqlSymFind sf{a->agent, name, &k, 0};
     loader.hsa_ven_amd_loader_iterate_executables(aql_on_executable, &sf);
     if (sf.hits != 1) return std::string("kernel symbol ") + name + (sf.hits ? " is loaded more than once" : " not found among the loaded executables");
     // the kernels read no hidden arguments (no blockDim / gridDim / printf): their kernarg segment ends with the explicit arguments. A
     // kernel that grew one would read garbage from a block filled like this, so that is refused here rather than dispatched.
-    if (k.kernarg != plan.k[i].size) {
+    const uint32_t want = plan.k[tw ? plan.n - 1 : i].size;
+    if (k.kernarg != want) {
       char m[256];
-      snprintf(m, sizeof m, "kernel %s: kernarg segment %u B, explicit arguments %u B (hidden arguments are not filled on this path)", name, k.kernarg, plan.k[i].size);
+      snprintf(m, sizeof m, "kernel %s: kernarg segment %u B, explicit arguments %u B (hidden arguments are not filled on this path)", name, k.kernarg, want);
       return m;
     }
   }
@@ -162,7 +175,7 @@ static std::string aql_dispatch(AqlState* a, const StepPlan& plan, int set) {
   if (plan.n != a->nkern) return "the step's kernels changed after the AQL set-up";
   unsigned char* blk = a->d_args + (size_t)set * 2 * KLaunch::kCap;
   for (int i = 0; i < plan.n; ++i)
-    if (plan.k[i].fn != a->kern[i].fn) return "the step's kernels changed after the AQL set-up";
+    if (!aql_kern(a, i, plan.k[i].fn)) return "the step's kernels changed after the AQL set-up";
   bool same = a->have_block[set];
   for (int i = 0; i < plan.n && same; ++i) same = memcmp(a->cached[set][i], plan.k[i].args, plan.k[i].size) == 0;
   if (!same) {   // first use of the set, or a buffer behind it was reallocated
@@ -179,7 +192,7 @@ static std::string aql_dispatch(AqlState* a, const StepPlan& plan, int set) {
   uint32_t hdr[2];
   for (int i = 0; i < plan.n; ++i) {
     const KLaunch& k = plan.k[i];
-    const AqlState::Kern& kk = a->kern[i];
+    const AqlState::Kern& kk = *aql_kern(a, i, plan.k[i].fn);
     hsa_kernel_dispatch_packet_t* p = (hsa_kernel_dispatch_packet_t*)q->base_address + ((idx + i) & (q->size - 1));
     memset((char*)p + 4, 0, sizeof *p - 4);   // (the header word stays INVALID until the body is complete)
     p->workgroup_size_x = (uint16_t)k.block.x; p->workgroup_size_y = 1; p->workgroup_size_z = 1;

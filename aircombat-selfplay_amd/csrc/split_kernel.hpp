@@ -113,8 +113,55 @@ struct ActionFetch {
     return 0.0f;
   }
 };
+// Late actions (step_kernel_1v1<AC_TASK_SINGLECOMBAT, 1, 1, true>, launched only by ac_step_host_actions; late_actions.hpp has the host
+// half): the host rings the doorbell first and copies the rows into the mapped set under the launch, so a row may still be the set's
+// PREVIOUS one when this wave reads it. `late` is the set's header block in mapped host memory. Its first word, written before the
+// doorbell and fetched with a second hidden load beside the row (one address for the whole wave), says what to expect: 0 = plain rows,
+// taken as they are; 1 / 2 = the tag every row of this step carries in the two lowest mantissa bits of its fourth element. While a
+// lane's row does not carry it the wave sleeps and asks for the rows again, at system scope, at most as often as the block's third
+// word allows; then it reports AC_ERR_LATE_ACTIONS through the error word and flies the step on what it has. Only this wave has loads
+// in flight then (the other two wait at B2), and every re-issued load is waited for right behind it. Every other kernel keeps
+// ActionFetch: the kernel behind step_device and the plain host steps is compiled from the same text as before.
+#define AC_ERR_LATE_ACTIONS 1   // P.err: below every non-finite code (emit_scalars), so that one of those outranks it in the max
+struct LateActionFetch {
+  ActionRow idx;
+  ActionWord hdr;
+  const float* src;
+  int* late;
+  int* err;
+  __device__ __forceinline__ void issue(const float* act, int* late_hdr, int* err_word) {
+    src = act; late = late_hdr; err = err_word;
+    idx.issue(act);
+    hdr.issue(reinterpret_cast<const float*>(late_hdr));
+  }
+  __device__ __forceinline__ void issue_sys() { asm volatile("global_load_dwordx4 %0, %1, off sc0 sc1" : "=&v"(idx.v) : "v"(src) : "memory"); }
+  __device__ __forceinline__ void take() {
+    idx.take(); hdr.take();
+    const unsigned tag = (unsigned)__builtin_amdgcn_readfirstlane(__float_as_int(hdr.v));
+    if (tag == 0u) return;
+    if (__ballot(((unsigned)__float_as_int(idx.v.w) & 3u) != tag) != 0ull) {   // rare (a host thread held up behind the doorbell)
+      // the budget sits in the header block and is read only here: nothing the common path waits for
+      const int budget = __builtin_amdgcn_readfirstlane(*reinterpret_cast<volatile const int*>(late + 2));
+      int tries = 0;
+      do {
+        if (tries >= budget) {
+          if ((threadIdx.x & 63) == 0) __hip_atomic_fetch_max(err, AC_ERR_LATE_ACTIONS, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+          break;
+        }
+        tries += 1;
+        __builtin_amdgcn_s_sleep(8);
+        issue_sys();
+        idx.take();
+      } while (__ballot(((unsigned)__float_as_int(idx.v.w) & 3u) != tag) != 0ull);
+      if (tries != 0 && (threadIdx.x & 63) == 0) __hip_atomic_fetch_add(late + 1, tries, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+    idx.v.w = __int_as_float(__float_as_int(idx.v.w) & ~3);
+  }
+  __device__ __forceinline__ float packed() const { return 0.0f; }   // (act_dim 4: nothing behind the control indices)
+};
+template <class ROW = ActionFetch>
 __device__ __forceinline__ void systems_wave(f16::State& s, Task& t, const f16::Tab& T, float (*M)[64], int l, int substeps, const float4* raw = nullptr,
-                                             ActionFetch* row = nullptr) {
+                                             ROW* row = nullptr) {
   using namespace mail;
   f16::DynVars km{};
   f16::sys_mass(s, km);
@@ -265,9 +312,9 @@ struct SplitLds {
 };
 // Helper waves of a three-wave workgroup: run their part of every substep and return true (the caller returns); the dynamics
 // wave (wave 0) gets false. Commands (s.da .. s.thr) must be decoded before the call, or handed over as the raw action row.
-template <bool QUAD = false, bool POSE = false>
+template <bool QUAD = false, bool POSE = false, class ROW = ActionFetch>
 __device__ __forceinline__ bool split_helper_wave(f16::State& s, Task& t, const f16::Tab& T, SplitLds& L, int l, int substeps, const float4* raw = nullptr,
-                                                  const DevCfg* cfg = nullptr, ActionFetch* row = nullptr) {
+                                                  const DevCfg* cfg = nullptr, ROW* row = nullptr) {
   const int role = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   if (role == 2) { kinematics_wave<QUAD, POSE>(s, t, T, L.M, L.MD, l, substeps, cfg); return true; }   // (a caller with work left for this wave tests the role itself)
   if (role == 1) { systems_wave(s, t, T, L.M, l, substeps, raw, row); return true; }

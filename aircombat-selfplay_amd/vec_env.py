@@ -258,7 +258,7 @@ class HipVecEnv:
         self._actions = self._sets[0]["actions"]
         # what step() hands back for each set, built once: the arrays are views of fixed buffers, and LazyInfos reads its codes when asked
         self._results = [self._result(st) for st in self._sets]
-        self._step_host = self.lib.ac_step_host
+        self._step_host = self.lib.ac_step_host_actions
         self._ref0 = self._refs(self._sets[0])   # what a set's arrays count when only this object holds them
 
     def _add_set(self):
@@ -385,9 +385,19 @@ class HipVecEnv:
     def step(self, actions):
         """VecEnv.step = step_async + step_wait (env_wrappers.py:30-42), through one library call."""
         assert not self.closed, "Trying to operate on a HipVecEnv after calling close()"
-        st, staged = self._hand_over(actions)
-        if self._step_host(self._h, st["index"]) != 0:
-            self.lib.check(-1, "ac_step_host")      # RuntimeError: a HIP failure, or a non-finite aircraft state ("JSBSim failed.")
+        st, staged = self._next_set()
+        # the library copies the batch into the set itself, where the kernel form allows under the launch (ac_step_host_actions)
+        a = actions
+        if not (isinstance(a, np.ndarray) and a.dtype == np.float32 and a.flags.c_contiguous):
+            a = np.ascontiguousarray(actions, dtype=np.float32)
+        if a.size != self._actions.size:
+            a = a.reshape(self._actions.shape)    # (raises like the copy into the set's buffer would)
+        try:
+            addr = C.addressof(C.c_char.from_buffer(a))
+        except (TypeError, ValueError):           # a read-only array
+            addr = a.ctypes.data
+        if self._step_host(self._h, st["index"], addr, a.size) != 0:
+            self.lib.check(-1, "ac_step_host_actions")      # RuntimeError: a HIP failure, a non-finite aircraft state ("JSBSim failed."), or rows that never arrived
         return self._returned(st, staged)
 
     def render(self, mode="txt", filepath="./JSBSimRecording.txt.acmi", env=0):

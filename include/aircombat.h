@@ -22,6 +22,7 @@
  */
 #ifndef AIRCOMBAT_H
 #define AIRCOMBAT_H
+#include <stddef.h>
 #include <stdint.h>
 #ifdef __cplusplus
 extern "C" {
@@ -145,6 +146,38 @@ void ac_host_set_free(void* actions, void* obs, void* rewards, void* dones, void
 int ac_step_host_async(ac_env_t* h, int32_t set);
 int ac_step_host_wait(ac_env_t* h);
 int ac_step_host(ac_env_t* h, int32_t set);   /* both in one call: VecEnv.step (env_wrappers.py:30-42) */
+/* The same step from the caller's own array (`n_floats` = envs x agents x act_dim floats, any alignment): the library copies it into
+ * set `set`. For the three-wave SingleCombat kernel (act_dim 4) on the AQL path the order is header word, doorbell, copy, wait: a share
+ * (ac_late_config's `fraction`) of the rows crosses into the mapped buffer UNDER the launch. Each 16-byte row then carries a two-bit
+ * tag (1 / 2, alternating per use of the set) in the two lowest mantissa bits of its fourth element, which the kernel checks and
+ * masks: a throttle index whose two trailing mantissa bits are zero (every integer below 2^22) arrives bit-exact, any other is
+ * rounded toward zero by at most 3 ulp. A systems wave whose rows do not carry the step's tag sleeps and asks again, at most `budget`
+ * times; then the call returns -1 ("... did not reach the device within the retry budget ...") and every later step does until
+ * ac_reset. Every other kernel form, and a handle off the AQL path, copies first, untagged, and then behaves like ac_step_host. */
+int ac_step_host_actions(ac_env_t* h, int32_t set, const float* actions, size_t n_floats);
+#define AC_LATE_FRACTION_DEFAULT 1.0    /* share of the batch copied behind the doorbell (profiles/late_actions_summary.txt) */
+#define AC_LATE_BUDGET_DEFAULT 400000   /* tries of ~1.6 us each (a sleep and a read across PCIe): 0.6 s, well under the 10 s AQL deadline */
+#define AC_LATE_WINDOW 1024                  /* late steps per window of the self-check */
+#define AC_LATE_WINDOW_MAX_RETRY_STEPS 16    /* retrying steps a window may hold: five times what a held-up host thread was seen to cause */
+typedef struct {
+  int64_t steps;          /* steps taken the late way */
+  int64_t retries;        /* row loads the systems waves re-issued, over all of them ... */
+  int32_t last_retries;   /* ... and in the last one */
+  int32_t last_late;      /* 1: the last host step went the late way */
+  int64_t retry_steps;    /* steps in which any load was re-issued */
+  int64_t lowered;        /* how often the self-check moved a quarter of the batch back in front of the doorbell ... */
+  int64_t disabled;       /* ... and 1 once nothing was left behind it: the handle is back on copy-first */
+  double fraction;        /* the share copied behind the doorbell now */
+  int64_t timed_steps;    /* while `timing` is on: steps in, and microseconds summed into, the four fields below */
+  double copy_before_us, dispatch_us, copy_after_us, wait_us;   /* header + rows in front of the doorbell; packet + doorbell; rows behind it; wait */
+} ac_late_stats_t;
+/* Self-check: when more than AC_LATE_WINDOW_MAX_RETRY_STEPS of AC_LATE_WINDOW consecutive late steps had a wave ask again, the copy does
+ * not fit under the launch on this host: `fraction` drops by a quarter, and at 0 the handle goes back to copy-first (the plain kernel),
+ * until ac_late_config sets `fraction` again.
+ * fraction in 0 .. 1, budget in tries, delay_us: a pause between doorbell and copy (tests: nothing else makes the kernel retry), timing 0 / 1;
+ * a negative value leaves that parameter as it is. */
+int ac_late_config(ac_env_t* h, double fraction, int32_t budget, int32_t delay_us, int32_t timing);
+int ac_late_stats(ac_env_t* h, ac_late_stats_t* out);
 
 /* Device-resident variant of the same step: d_actions is a DEVICE pointer (or NULL to use the
  * handle's own action buffer); results stay in the handle's device buffers; asynchronous on the handle's stream. */

@@ -1,6 +1,9 @@
 #!/usr/bin/env python3
 """Where a VecEnv.step(numpy) of the headline config (or: <envs> <task> <per_side>) spends its time on the host: the action copy into the mapped buffer, the launch
-call, the wait. (time.perf_counter_ns around the three pieces; ~0.1 us of timer overhead each.)"""
+call, the wait. (time.perf_counter_ns around the three pieces; ~0.1 us of timer overhead each.) Then VecEnv.step's own order -- header word,
+doorbell, copy under the launch, wait (ac_step_host_actions) -- timed inside the library, with the kernel's retry counter, for the
+library's share of the copy behind the doorbell or for every share of a comma-separated fourth argument."""
+import ctypes as C
 import os
 import sys
 import time
@@ -48,4 +51,28 @@ t0 = now()
 for it in range(3000):
     env.step(acts[it & 15])
 print(f"VecEnv.step: {(now() - t0) / 3000 / 1e3:.2f} us/step")
+# VecEnv.step through ac_step_host_actions, piece by piece as the library times them (ac_late_config's timing), for each share f of the
+# batch copied behind the doorbell: the copy time hidden under the wait is `copy after`, and `retries` counts the row loads the kernel
+# re-issued over the run (a path that retries in steady state is not one to ship). Fourth argument: the shares to sweep.
+fractions = [float(x) for x in sys.argv[4].split(",")] if len(sys.argv) > 4 else [pkg.capi.AC_LATE_FRACTION_DEFAULT]
+lib = env.lib
+for f in fractions:
+    lib.check(lib.ac_late_config(h, f, -1, -1, 0), "ac_late_config")
+    for it in range(300):
+        env.step(acts[it & 15])
+    before = pkg.capi.AcLateStats()
+    lib.check(lib.ac_late_stats(h, C.byref(before)), "ac_late_stats")
+    lib.check(lib.ac_late_config(h, -1.0, -1, -1, 1), "ac_late_config")
+    K = 2000
+    t0 = now()
+    for it in range(K):
+        env.step(acts[it & 15])
+    dt = (now() - t0) / K / 1e3
+    st = pkg.capi.AcLateStats()
+    lib.check(lib.ac_late_stats(h, C.byref(st)), "ac_late_stats")
+    n = max(1, st.timed_steps - before.timed_steps)
+    d = lambda name: (getattr(st, name) - getattr(before, name)) / n
+    print(f"late actions f={f:.3f}: {st.steps - before.steps} late steps of {K}, retries {st.retries - before.retries} in {st.retry_steps - before.retry_steps} steps   "
+          f"copy before {d('copy_before_us'):.2f} us  dispatch {d('dispatch_us'):.2f} us  copy after (under the wait) {d('copy_after_us'):.2f} us  "
+          f"wait {d('wait_us'):.2f} us   VecEnv.step {dt:.2f} us/step")
 env.close()
