@@ -876,7 +876,11 @@ void f16_tick(F16State* s, double dt) {
 }
 
 void f16_refresh_derived(F16State* s) {
-  s->sim_time = (double)s->ticks / 60.0;
+  /* the clock is the running fp64 sum of dT (IncrTime above), not ticks / 60: 600 additions of 1/60 already exceed 10, which is what
+   * Overload's "sim-time-sec > 10" sees at tick 600; an imported state must see the same. O(ticks) per import (the suite imports
+   * states of at most a few thousand ticks); 60 Hz like the ticks / 60 it replaces: the bridge has no dt to read */
+  s->sim_time = 0.0;
+  for (long k = 0; k < s->ticks; k++) s->sim_time += 1.0 / 60.0;
   s->epa = OMEGA_E * s->sim_time;
   propagate_derived(s);
   massbalance_run(s); /* first call rebuilds the CG from the tanks, second the inertia about it */
