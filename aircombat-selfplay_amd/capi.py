@@ -376,6 +376,10 @@ SIGNATURES = {
     "ac_buffer_epoch_layout_for": (C.c_int, [C.POINTER(AcBufferConfig), C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "ac_buffer_gather_epoch": (C.c_int, [_p, _p, _p, C.c_int32, C.c_int32, C.c_int32, _p]),
     "ac_buffer_epoch_source_row_host": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "ac_buffers_epoch_layout": (C.c_int, [C.POINTER(_p), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "ac_buffers_gather_epoch": (C.c_int, [C.POINTER(_p), C.c_int32, _p, _p, C.c_int32, C.c_int32, C.c_int32, _p]),
+    "ac_buffers_minibatch": (C.c_int, [C.POINTER(_p), C.c_int32, _p, C.c_int32, C.c_int32, C.POINTER(AcBufferBatch), C.c_int]),
+    "ac_buffers_epoch_source_host": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
     # include/aircombat_rollout.h
     "ac_rollout_create": (C.c_int, [_p, _p, _p, _p, _p, C.POINTER(_p)]),
     "ac_rollout_destroy": (C.c_int, [_p]),

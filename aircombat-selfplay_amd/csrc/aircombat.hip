@@ -3022,6 +3022,7 @@ int ac_get_missile_target(ac_env_t* h, int32_t env, int32_t agent, int32_t k, in
 #include "snapshot.hpp"
 #include "rollout_buffer.hpp"
 #include "epoch_gather.hpp"
+#include "epoch_gather_multi.hpp"
 #include "policy_kernel.hpp"
 #include "policy_host.hpp"
 #include "policy_pool.hpp"

@@ -254,10 +254,26 @@ class DevicePPOTrainer:
         return stats[capi.AC_PPO_STAT_POLICY_LOSS], stats[capi.AC_PPO_STAT_VALUE_LOSS], stats[capi.AC_PPO_STAT_ENTROPY_LOSS], \
             stats[capi.AC_PPO_STAT_RATIO_MEAN], norms[0], norms[1]
 
+    @staticmethod
+    def _device_list(buffer):
+        """The list of two or more device buffers ``buffer`` is, or None (one buffer, or only the reference's host buffers). A list
+        that mixes host and device buffers is a ValueError: the two gather in different places."""
+        from .rollout_buffer import DeviceReplayBuffer
+        if not isinstance(buffer, (list, tuple)) or len(buffer) < 2:
+            return None
+        on_device = [isinstance(b, DeviceReplayBuffer) for b in buffer]
+        if any(on_device) and not all(on_device):
+            raise ValueError("train: a list that mixes the reference's host buffers with device buffers (train on one kind: the host "
+                             "buffers gather on the host, the device buffers in one launch)")
+        return list(buffer) if all(on_device) else None
+
     def _generator(self, buffer, chunk_order=None):
         from .rollout_buffer import DeviceReplayBuffer, DeviceSharedReplayBuffer
-        one = buffer[0] if isinstance(buffer, (list, tuple)) and len(buffer) == 1 else buffer
         n, L = self.num_mini_batch, self.data_chunk_length
+        several = self._device_list(buffer)
+        if several is not None:   # the list form, for both buffer classes
+            return DeviceReplayBuffer.recurrent_generator(several, n, L, chunk_order=chunk_order, on_device=True)
+        one = buffer[0] if isinstance(buffer, (list, tuple)) and len(buffer) == 1 else buffer
         if isinstance(one, DeviceSharedReplayBuffer):
             return one.recurrent_generator(None, n, L, chunk_order=chunk_order, on_device=True)
         if isinstance(one, DeviceReplayBuffer):
@@ -271,6 +287,9 @@ class DevicePPOTrainer:
     def _epoch(self, buffer, chunk_order=None):
         """One epoch's minibatches of a device buffer from one launch (``buffer.epoch``), no host wait."""
         from .rollout_buffer import DeviceReplayBuffer
+        several = self._device_list(buffer)
+        if several is not None:   # one launch over the stack of the list's buffers
+            return DeviceReplayBuffer.epoch_of(several, self.num_mini_batch, self.data_chunk_length, chunk_order=chunk_order)
         one = buffer[0] if isinstance(buffer, (list, tuple)) and len(buffer) == 1 else buffer
         if not isinstance(one, DeviceReplayBuffer):
             raise ValueError("train: stream_ordered minibatches need a DeviceReplayBuffer / DeviceSharedReplayBuffer (the reference's buffers gather on the host)")
@@ -280,7 +299,10 @@ class DevicePPOTrainer:
         """The reference's ``train``: ppo_epoch passes over num_mini_batch minibatches, and the same ``train_info`` dict with the same
         averaging. Every minibatch's six scalars go to one row of a device tensor that is read once at the end. ``buffer`` is one of
         the reference's buffers or a DeviceReplayBuffer / DeviceSharedReplayBuffer (asked for ``on_device=True``). ``chunk_orders``
-        (tests): one chunk permutation per epoch for a device buffer instead of torch.randperm.
+        (tests): one chunk permutation per epoch for a device buffer instead of torch.randperm. ``buffer`` may also be a list of up to
+        8 device buffers of one shape (``DeviceReplayBuffer.recurrent_generator`` / ``epoch_of`` of the list, on either path: one
+        permutation over the stack of their sequence views, as the reference's generator treats a list of its buffers); a list that
+        mixes host and device buffers is a ValueError.
 
         ``stream_ordered`` (None: ``args.use_stream_ordered_minibatches``, absent: False): each epoch is one ``buffer.epoch(...)`` on
         torch's current stream instead of the generator, whose every minibatch waits for the device twice; the read at the end is

@@ -211,6 +211,11 @@ class DeviceReplayBuffer:
         The gather runs on the buffer's own stream. Torch's caching allocator may hand out memory that work queued on torch's
         current stream still reads, so that stream is waited for first; the gather then ends with a wait for the buffer's stream,
         and the tensors are complete, safe to read on any stream, when they are returned."""
+        return self._minibatch([self], chunks, data_chunk_length, on_device)
+
+    def _minibatch(self, buffers, chunks, data_chunk_length, on_device):
+        """``minibatch`` for chunk indices into the stack of ``buffers`` (``self`` is its first): ``[self]`` goes through the
+        single-handle call, a longer list through the list call."""
         chunks = np.ascontiguousarray(chunks, dtype=np.int32)
         n, L = len(chunks), int(data_chunk_length)
         widths = {"obs": self.obs_shape, "share_obs": self.share_obs_shape, "actions": self.act_shape, "masks": (1,), "active_masks": (1,),
@@ -227,8 +232,29 @@ class DeviceReplayBuffer:
         else:
             outs = {k: np.empty(s, dtype=np.float32) for k, s in shapes.items()}
             batch = AcBufferBatch(**{k: v.ctypes.data for k, v in outs.items()})
-        self._ok(self.lib.ac_buffer_minibatch(self._h, chunks.ctypes.data, n, L, C.byref(batch), int(bool(on_device))), "ac_buffer_minibatch")
+        if len(buffers) == 1:
+            self._ok(self.lib.ac_buffer_minibatch(self._h, chunks.ctypes.data, n, L, C.byref(batch), int(bool(on_device))), "ac_buffer_minibatch")
+        else:
+            self._ok(self.lib.ac_buffers_minibatch(_handles(buffers), len(buffers), chunks.ctypes.data, n, L, C.byref(batch), int(bool(on_device))),
+                     "ac_buffers_minibatch")
         return tuple(outs[k] for k in self._BATCH) + (outs["rnn_states_actor"], outs["rnn_states_critic"])
+
+    @staticmethod
+    def epoch_of(buffers, num_mini_batch, data_chunk_length, chunk_order=None):
+        """``epoch`` over a list of up to 8 device buffers of one shape, as the reference's ``recurrent_generator`` treats a list of
+        buffers (buffer.py:183-214): the buffers' sequence views are stacked in the list's order and one chunk order runs over the
+        stack, ``data_chunks = n_rollout_threads * (buffer_size * K) // data_chunk_length`` chunks (the reference's formula: the agent
+        axis is not counted), so every mini-batch mixes rows of every buffer and a chunk may straddle two of them. One flat tensor,
+        ``queue_advantages()`` on every buffer (each buffer's advantages are normalised on its own, as the reference does) and then ONE
+        gather launch, all on torch's current stream with nothing waited for. ``chunk_order`` is ``epoch``'s, its indices chunks of
+        the stack. A list of one buffer gives ``buffer.epoch(...)`` bit for bit.
+
+        A list of ``DeviceSharedReplayBuffer`` is taken the same way: the reference's MAPPO generator has no list form, so this is the
+        PPO list rule applied to the shared buffer's fields (``share_obs`` and ``active_masks`` are stacked like ``obs`` and ``masks``).
+        ``ValueError`` for anything in the list that is no device buffer; buffers that differ in shape, class or device, the same
+        buffer twice and more than 8 buffers are refused by the library with the cause named, before anything is queued."""
+        buffers = _buffer_list(buffers, "epoch_of")
+        return buffers[0]._epoch(buffers, num_mini_batch, data_chunk_length, chunk_order, True)
 
     def epoch(self, num_mini_batch, data_chunk_length, chunk_order=None):
         """Every mini-batch of one pass of ``recurrent_generator(..., on_device=True)`` as a ``DeviceEpoch``, without a host wait: one
@@ -243,14 +269,23 @@ class DeviceReplayBuffer:
         ``minibatch`` checks its chunks and sent through pinned memory without blocking. An integer tensor on the buffer's GPU is
         used as it is, unchecked: the kernel clamps every index into the valid range, which keeps a bad index from reading
         outside the buffer but does not report it."""
+        return self._epoch([self], num_mini_batch, data_chunk_length, chunk_order, False)
+
+    def _epoch(self, buffers, num_mini_batch, data_chunk_length, chunk_order, as_list):
+        """``epoch`` (the single-handle calls) or, ``as_list``, ``epoch_of`` (the list calls) over ``buffers``, whose first is ``self``."""
         import torch
+        K = len(buffers)
         n_mb, L = int(num_mini_batch), int(data_chunk_length)
-        assert self.n_rollout_threads * self.buffer_size >= L, "PPO requires n_rollout_threads * buffer_size >= data_chunk_length"
-        data_chunks = self.n_rollout_threads * self.buffer_size // L
+        assert self.n_rollout_threads * self.buffer_size * K >= L, "PPO requires n_rollout_threads * buffer_size >= data_chunk_length"
+        data_chunks = self.n_rollout_threads * (self.buffer_size * K) // L
         mb = data_chunks // n_mb
         if n_mb < 1 or mb < 1:
             raise ValueError(f"epoch: {data_chunks} chunks do not fill {n_mb} mini-batches")
         dev, used = torch.device("cuda", self.device_id), n_mb * mb
+        offsets, total = (C.c_int64 * AC_EPOCH_NFIELDS)(), C.c_int64()
+        if as_list:   # the list's refusals (shapes, classes, devices, a handle twice) come before anything is drawn or queued
+            handles = _handles(buffers)
+            self._ok(self.lib.ac_buffers_epoch_layout(handles, K, n_mb, mb, L, offsets, C.byref(total)), "ac_buffers_epoch_layout")
         with torch.cuda.device(dev):
             if chunk_order is None:
                 order = torch.randperm(data_chunks, device=dev)[:used].to(torch.int32)
@@ -262,18 +297,23 @@ class DeviceReplayBuffer:
                 host = np.ascontiguousarray(np.asarray(chunk_order).reshape(-1)[:used], dtype=np.int32)
                 if host.size < used:
                     raise ValueError(f"epoch: chunk_order holds {host.size} indices, {used} are needed")
-                rows = self.buffer_size * self.n_rollout_threads * self.num_agents
+                rows = self.buffer_size * K * self.n_rollout_threads * self.num_agents
                 if (host < 0).any() or ((host.astype(np.int64) + 1) * L > rows).any():
                     raise RuntimeError("epoch failed: chunk index outside the buffer")
                 pinned = torch.empty(used, dtype=torch.int32, pin_memory=True)
                 pinned.numpy()[:] = host
                 order = pinned.to(dev, non_blocking=True)   # torch's host allocator orders the reuse of `pinned` after the copy
-            offsets, total = (C.c_int64 * AC_EPOCH_NFIELDS)(), C.c_int64()
-            self._ok(self.lib.ac_buffer_epoch_layout(self._h, n_mb, mb, L, offsets, C.byref(total)), "ac_buffer_epoch_layout")
+            if not as_list:
+                self._ok(self.lib.ac_buffer_epoch_layout(self._h, n_mb, mb, L, offsets, C.byref(total)), "ac_buffer_epoch_layout")
             flat = torch.empty(total.value, dtype=torch.float32, device=dev)
-            self.queue_advantages()
-            self._ok(self.lib.ac_buffer_gather_epoch(self._h, self._current_stream(), order.data_ptr(), n_mb, mb, L, flat.data_ptr()),
-                     "ac_buffer_gather_epoch")
+            for b in buffers:
+                b.queue_advantages()
+            if as_list:
+                self._ok(self.lib.ac_buffers_gather_epoch(handles, K, self._current_stream(), order.data_ptr(), n_mb, mb, L, flat.data_ptr()),
+                         "ac_buffers_gather_epoch")
+            else:
+                self._ok(self.lib.ac_buffer_gather_epoch(self._h, self._current_stream(), order.data_ptr(), n_mb, mb, L, flat.data_ptr()),
+                         "ac_buffer_gather_epoch")
         widths = {"obs": self.obs_shape, "share_obs": self.share_obs_shape, "actions": self.act_shape, "masks": (1,), "active_masks": (1,),
                   "action_log_probs": self._shapes["action_log_probs"][3:], "advantages": (1,), "returns": (1,), "value_preds": (1,)}
         hid = (self.recurrent_hidden_layers, self.recurrent_hidden_size)
@@ -291,26 +331,49 @@ class DeviceReplayBuffer:
 
     @staticmethod
     def recurrent_generator(buffer, num_mini_batch, data_chunk_length, chunk_order=None, on_device=False):
-        """ReplayBuffer.recurrent_generator(buffer, num_mini_batch, data_chunk_length) (buffer.py:169-268) for one buffer: the
-        chunk permutation comes from torch.randperm like the reference's unless ``chunk_order`` is given (tests). The number of
+        """ReplayBuffer.recurrent_generator(buffer, num_mini_batch, data_chunk_length) (buffer.py:169-268): the chunk permutation
+        comes from torch.randperm (the CPU generator) like the reference's unless ``chunk_order`` is given (tests). The number of
         chunks follows the reference: n_rollout_threads * buffer_size // data_chunk_length (the agent axis is not counted).
-        on_device=True yields torch tensors on the buffer's GPU instead of numpy arrays (``minibatch``)."""
-        self = buffer
-        if isinstance(buffer, (list, tuple)):
-            if len(buffer) != 1:
-                raise NotImplementedError("one device buffer per generator (the reference's list form concatenates host arrays)")
-            self = buffer[0]
-        L = int(data_chunk_length)
-        assert self.n_rollout_threads * self.buffer_size >= L, "PPO requires n_rollout_threads * buffer_size >= data_chunk_length"
-        data_chunks = self.n_rollout_threads * self.buffer_size // L
-        mb = data_chunks // int(num_mini_batch)
+        on_device=True yields torch tensors on the buffer's GPU instead of numpy arrays (``minibatch``).
+
+        ``buffer`` is one device buffer or, as in the reference, a list of up to 8 of one shape: their sequence views are stacked in
+        the list's order (the reference's np.vstack), ``buffer_size`` counts K times in the number of chunks, each buffer's
+        advantages are normalised on its own, and one permutation over the stack's chunks cuts mini-batches that mix rows of every
+        buffer (a chunk may straddle two of them). A list of ``DeviceSharedReplayBuffer`` is taken the same way: the reference's MAPPO
+        generator has no list form, so this is the PPO list rule applied to the shared buffer's fields. See ``epoch_of`` for what a
+        list is refused for."""
+        buffers = _buffer_list(buffer, "recurrent_generator")
+        self, K = buffers[0], len(buffers)
+        L, n_mb = int(data_chunk_length), int(num_mini_batch)
+        assert self.n_rollout_threads * self.buffer_size * K >= L, "PPO requires n_rollout_threads * buffer_size >= data_chunk_length"
+        data_chunks = self.n_rollout_threads * (self.buffer_size * K) // L
+        mb = data_chunks // n_mb
+        if K > 1:   # the list's refusals before anything runs
+            offsets, total = (C.c_int64 * AC_EPOCH_NFIELDS)(), C.c_int64()
+            self._ok(self.lib.ac_buffers_epoch_layout(_handles(buffers), K, n_mb, max(mb, 1), L, offsets, C.byref(total)), "ac_buffers_epoch_layout")
         if chunk_order is None:
             import torch
             chunk_order = torch.randperm(data_chunks).numpy()
         chunk_order = np.asarray(chunk_order)
-        self._ok(self.lib.ac_buffer_advantages(self._h), "ac_buffer_advantages")
-        for i in range(int(num_mini_batch)):
-            yield self.minibatch(chunk_order[i * mb:(i + 1) * mb], L, on_device=on_device)
+        for b in buffers:
+            b._ok(b.lib.ac_buffer_advantages(b._h), "ac_buffer_advantages")
+        for i in range(n_mb):
+            yield self._minibatch(buffers, chunk_order[i * mb:(i + 1) * mb], L, on_device)
+
+
+def _buffer_list(buffers, what):
+    """One device buffer or a list / tuple of them as a list; ValueError for an empty list or anything else in it (the reference's host
+    buffers among them: they gather on the host)."""
+    buffers = list(buffers) if isinstance(buffers, (list, tuple)) else [buffers]
+    if not buffers or not all(isinstance(b, DeviceReplayBuffer) for b in buffers):
+        raise ValueError(f"{what}: a DeviceReplayBuffer / DeviceSharedReplayBuffer or a list of them is needed, got "
+                         f"[{', '.join(type(b).__name__ for b in buffers)}]")
+    return buffers
+
+
+def _handles(buffers):
+    """The C array of the buffers' handles (a closed buffer's is NULL, which the library refuses)."""
+    return (C.c_void_p * len(buffers))(*[b._h for b in buffers])
 
 
 class DeviceSharedReplayBuffer(DeviceReplayBuffer):

@@ -62,6 +62,42 @@ int ac_buffer_gather_epoch(ac_buffer_t* b, void* caller, const int32_t* d_order,
  * [0, chunk_len). */
 int64_t ac_buffer_epoch_source_row_host(int32_t chunk, int32_t l, int32_t chunk_len, int32_t T, int32_t N);
 
+/* ---- The list form: mini-batches cut from K buffers of one shape, as ReplayBuffer.recurrent_generator does for a list of buffers
+ * (algorithms/utils/buffer.py:183-214). The buffers' column-major sequence views are stacked in the order of `bufs`: row R of the stack
+ * is row R % (T * N) of buffer R / (T * N). Chunk c covers rows [c * chunk_len, (c + 1) * chunk_len) of the stack, so that a chunk may
+ * straddle two columns and, where chunk_len does not divide T * N, two buffers; the RNN fields take the row of the chunk's first step,
+ * from the buffer that row lies in. One permutation over the K * T * N / chunk_len chunks then mixes rows of every buffer in every
+ * mini-batch. The advantages are each buffer's own (normalised per buffer, as the reference normalises them): queue them per handle
+ * before the gather. The single-handle calls above are untouched by these; K = 1 gives what they give.
+ *
+ * Refused by every call below that takes `bufs`, with the cause named and nothing queued: a NULL `bufs` or handle, K outside
+ * 1 .. AC_EPOCH_MAX_BUFFERS, the same handle twice, buffers that differ in buffer_size, n_envs, n_agents, a field's width or in
+ * being shared (share_obs_dim > 0) or not, buffers on different devices, and (the gather) on another device than `caller`'s. */
+#define AC_EPOCH_MAX_BUFFERS 8
+
+/* The single form's layout rules over the stack's K * T * N rows. Refused as well: a NULL argument, non-positive sizes,
+ * n_minibatch * mb > K * T * N / chunk_len, a stack of more than 2^31 - 1 chunks. */
+int ac_buffers_epoch_layout(ac_buffer_t* const* bufs, int32_t K, int32_t n_minibatch, int32_t mb, int32_t chunk_len,
+                            int64_t offsets[AC_EPOCH_NFIELDS], int64_t* total_floats);
+
+/* One launch on `caller` for every field of every mini-batch of an epoch over the stack, into d_out as laid out above; d_order as in
+ * the single form, its indices clamped into [0, K * T * N / chunk_len - 1] before use (memory safety, not validation). On entry
+ * `caller` is made to wait for every buffer's own stream, on return every buffer's stream for `caller`; nothing is waited for on the
+ * host. */
+int ac_buffers_gather_epoch(ac_buffer_t* const* bufs, int32_t K, void* caller, const int32_t* d_order, int32_t n_minibatch, int32_t mb,
+                            int32_t chunk_len, float* d_out);
+
+/* The blocking form: one mini-batch of n_chunks chunks of the stack (host indices, checked: one outside the stack is refused) into the
+ * arrays of `batch` (NULL members are skipped), host arrays or with on_device device arrays. It waits for every buffer's stream, runs
+ * the same kernel on the first buffer's and returns when the arrays are complete. */
+int ac_buffers_minibatch(ac_buffer_t* const* bufs, int32_t K, const int32_t* chunks, int32_t n_chunks, int32_t chunk_len,
+                         const ac_buffer_batch_t* batch, int on_device);
+
+/* The list kernel's row function on the host (no GPU, no handle): step l of chunk `chunk` of a stack of K buffers of T steps and N
+ * columns lies in buffer *k at time-major source row *row = t * N + col, with the clamp applied to `chunk`. -1 for a NULL pointer,
+ * non-positive sizes, K outside 1 .. AC_EPOCH_MAX_BUFFERS, chunk_len > K * T * N or l outside [0, chunk_len). */
+int ac_buffers_epoch_source_host(int32_t chunk, int32_t l, int32_t chunk_len, int32_t T, int32_t N, int32_t K, int32_t* k, int64_t* row);
+
 #ifdef __cplusplus
 }
 #endif
