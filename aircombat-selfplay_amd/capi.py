@@ -339,6 +339,11 @@ SIGNATURES = {
     "ac_gru_layer_forward": (C.c_int, [C.c_int32, _p, C.c_int32, C.c_int32] + [_p] * 9 + [C.c_float] + [_p] * 6),
     "ac_gru_layer_backward": (C.c_int, [C.c_int32, _p, C.c_int32, C.c_int32] + [_p] * 20),
     "ac_gru_layer_constant": (C.c_int32, [C.c_int32]),
+    # the four calls above with `products` (AC_PRODUCTS_FP32 0, AC_PRODUCTS_BF16X3 1) as the last argument
+    "ac_gru_seq_forward_p": (C.c_int, [C.c_int32, _p, C.c_int32, C.c_int32, _p, _p, _p, _p, _p, _p, _p, _p, C.c_int32]),
+    "ac_gru_seq_backward_p": (C.c_int, [C.c_int32, _p, C.c_int32, C.c_int32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, C.c_int32]),
+    "ac_gru_layer_forward_p": (C.c_int, [C.c_int32, _p, C.c_int32, C.c_int32] + [_p] * 9 + [C.c_float] + [_p] * 6 + [C.c_int32]),
+    "ac_gru_layer_backward_p": (C.c_int, [C.c_int32, _p, C.c_int32, C.c_int32] + [_p] * 20 + [C.c_int32]),
     "ac_mlp_block_workspace_floats": (C.c_int64, [C.c_int32, C.c_int32]),
     "ac_mlp_block_forward": (C.c_int, [C.c_int32, _p, C.c_int32, C.c_int32, C.c_float, _p, _p, _p, _p, _p, _p, _p]),
     "ac_mlp_block_backward": (C.c_int, [C.c_int32, _p, C.c_int32, C.c_int32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),

@@ -380,39 +380,56 @@ int32_t ac_gru_layer_constant(int32_t which) {
   }
 }
 
-int ac_gru_layer_forward(int32_t device_id, void* stream, int32_t N, int32_t T, const float* d_x, const float* d_hxs, const float* d_masks,
-                         const float* d_w_ih, const float* d_w_hh, const float* d_b_ih, const float* d_b_hh, const float* d_gamma,
-                         const float* d_beta, float eps, float* d_workspace, float* d_out, float* d_h_T, float* d_y, float* d_saved,
-                         float* d_stats) {
+// `who` names the entry in its refusals; `products` (checked by the caller) selects the recurrence kernel alone
+static int gru_layer_forward(const std::string& who, int32_t products, int32_t device_id, void* stream, int32_t N, int32_t T, const float* d_x,
+                             const float* d_hxs, const float* d_masks, const float* d_w_ih, const float* d_w_hh, const float* d_b_ih,
+                             const float* d_b_hh, const float* d_gamma, const float* d_beta, float eps, float* d_workspace, float* d_out,
+                             float* d_h_T, float* d_y, float* d_saved, float* d_stats) {
   if (!d_x || !d_hxs || !d_masks || !d_w_ih || !d_w_hh || !d_b_ih || !d_b_hh || !d_gamma || !d_beta || !d_workspace || !d_out || !d_h_T || !d_y)
-    return fail("ac_gru_layer_forward: null argument");
-  if ((d_saved == nullptr) != (d_stats == nullptr)) return fail("ac_gru_layer_forward: saved and stats go together (both, or both NULL)");
-  if (gru_layer_shape_ok("ac_gru_layer_forward", N, T)) return -1;
+    return fail(who + ": null argument");
+  if ((d_saved == nullptr) != (d_stats == nullptr)) return fail(who + ": saved and stats go together (both, or both NULL)");
+  if (gru_layer_shape_ok(who.c_str(), N, T)) return -1;
   if (!trn::aligned16({d_x, d_w_ih, d_gamma, d_beta, d_workspace, d_out, d_y, d_stats}))
-    return fail("ac_gru_layer_forward: x, w_ih, gamma, beta, workspace, out, y and stats must be 16-byte aligned");
+    return fail(who + ": x, w_ih, gamma, beta, workspace, out, y and stats must be 16-byte aligned");
   HIP_OK(hipSetDevice(device_id));
   const int M = N * T;
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(grul::gru_gi_fwd, dim3(trn::capped_tiles(M, grul::RT, grul::GI_WGS)), dim3(512), 0, s, d_x, d_w_ih, d_b_ih, d_workspace, M);
   HIP_OK(hipGetLastError());
-  hipLaunchKernelGGL(grut::gru_seq_fwd, dim3(trn::tiles(N, grut::RT)), dim3(512), 0, s, (const float*)d_workspace, d_hxs, d_masks, d_w_hh,
-                     d_b_hh, d_y, d_h_T, d_saved, (int)N, (int)T);
+  hipLaunchKernelGGL(products == AC_PRODUCTS_BF16X3 ? grus::gru_seq_fwd_b3 : grut::gru_seq_fwd, dim3(trn::tiles(N, grut::RT)), dim3(512), 0, s,
+                     (const float*)d_workspace, d_hxs, d_masks, d_w_hh, d_b_hh, d_y, d_h_T, d_saved, (int)N, (int)T);
   HIP_OK(hipGetLastError());
   hipLaunchKernelGGL(grul::gru_ln_fwd, dim3(trn::capped_tiles(M, grul::RT, grul::LN_WGS)), dim3(512), 0, s, (const float*)d_y, d_gamma, d_beta, d_out, d_stats, M, eps);
   HIP_OK(hipGetLastError());
   return 0;
 }
+int ac_gru_layer_forward(int32_t device_id, void* stream, int32_t N, int32_t T, const float* d_x, const float* d_hxs, const float* d_masks,
+                         const float* d_w_ih, const float* d_w_hh, const float* d_b_ih, const float* d_b_hh, const float* d_gamma,
+                         const float* d_beta, float eps, float* d_workspace, float* d_out, float* d_h_T, float* d_y, float* d_saved,
+                         float* d_stats) {
+  return gru_layer_forward("ac_gru_layer_forward", AC_PRODUCTS_FP32, device_id, stream, N, T, d_x, d_hxs, d_masks, d_w_ih, d_w_hh, d_b_ih, d_b_hh,
+                           d_gamma, d_beta, eps, d_workspace, d_out, d_h_T, d_y, d_saved, d_stats);
+}
+int ac_gru_layer_forward_p(int32_t device_id, void* stream, int32_t N, int32_t T, const float* d_x, const float* d_hxs, const float* d_masks,
+                           const float* d_w_ih, const float* d_w_hh, const float* d_b_ih, const float* d_b_hh, const float* d_gamma,
+                           const float* d_beta, float eps, float* d_workspace, float* d_out, float* d_h_T, float* d_y, float* d_saved,
+                           float* d_stats, int32_t products) {
+  if (gru_products_ok("ac_gru_layer_forward_p", products)) return -1;
+  return gru_layer_forward("ac_gru_layer_forward_p", products, device_id, stream, N, T, d_x, d_hxs, d_masks, d_w_ih, d_w_hh, d_b_ih, d_b_hh,
+                           d_gamma, d_beta, eps, d_workspace, d_out, d_h_T, d_y, d_saved, d_stats);
+}
 
-int ac_gru_layer_backward(int32_t device_id, void* stream, int32_t N, int32_t T, const float* d_g_out, const float* d_g_h_T, const float* d_x,
-                          const float* d_hxs, const float* d_masks, const float* d_w_ih, const float* d_w_hh, const float* d_gamma,
-                          const float* d_y, const float* d_saved, const float* d_stats, float* d_workspace, float* d_dx, float* d_dhxs,
-                          float* d_dw_ih, float* d_dw_hh, float* d_db_ih, float* d_db_hh, float* d_dgamma, float* d_dbeta) {
+static int gru_layer_backward(const std::string& who, int32_t products, int32_t device_id, void* stream, int32_t N, int32_t T, const float* d_g_out,
+                              const float* d_g_h_T, const float* d_x, const float* d_hxs, const float* d_masks, const float* d_w_ih,
+                              const float* d_w_hh, const float* d_gamma, const float* d_y, const float* d_saved, const float* d_stats,
+                              float* d_workspace, float* d_dx, float* d_dhxs, float* d_dw_ih, float* d_dw_hh, float* d_db_ih, float* d_db_hh,
+                              float* d_dgamma, float* d_dbeta) {
   if (!d_x || !d_hxs || !d_masks || !d_w_ih || !d_w_hh || !d_gamma || !d_y || !d_saved || !d_stats || !d_workspace || !d_dw_ih || !d_dw_hh ||
       !d_db_ih || !d_db_hh || !d_dgamma || !d_dbeta)
-    return fail("ac_gru_layer_backward: null argument");
-  if (gru_layer_shape_ok("ac_gru_layer_backward", N, T)) return -1;
+    return fail(who + ": null argument");
+  if (gru_layer_shape_ok(who.c_str(), N, T)) return -1;
   if (!trn::aligned16({d_g_out, d_x, d_hxs, d_gamma, d_y, d_stats, d_workspace, d_dx}))
-    return fail("ac_gru_layer_backward: g_out, x, hxs, gamma, y, stats, workspace and dx must be 16-byte aligned");
+    return fail(who + ": g_out, x, hxs, gamma, y, stats, workspace and dx must be 16-byte aligned");
   HIP_OK(hipSetDevice(device_id));
   const int M = N * T;
   const grul::Layout l = grul::layout(M);
@@ -428,8 +445,8 @@ int ac_gru_layer_backward(int32_t device_id, void* stream, int32_t N, int32_t T,
     HIP_OK(hipMemsetAsync(d_dgamma, 0, grul::H * sizeof(float), s));
     HIP_OK(hipMemsetAsync(d_dbeta, 0, grul::H * sizeof(float), s));
   }
-  hipLaunchKernelGGL(grut::gru_seq_bwd, dim3(trn::tiles(N, grut::RT)), dim3(512), 0, s, d_g_out ? (const float*)dy : nullptr, d_g_h_T, d_saved,
-                     d_y, d_hxs, d_masks, d_w_hh, dgi, dgh, d_dhxs, (int)N, (int)T);
+  hipLaunchKernelGGL(products == AC_PRODUCTS_BF16X3 ? grus::gru_seq_bwd_b3 : grut::gru_seq_bwd, dim3(trn::tiles(N, grut::RT)), dim3(512), 0, s,
+                     d_g_out ? (const float*)dy : nullptr, d_g_h_T, d_saved, d_y, d_hxs, d_masks, d_w_hh, dgi, dgh, d_dhxs, (int)N, (int)T);
   HIP_OK(hipGetLastError());
   hipLaunchKernelGGL(grul::gru_dw, dim3(2 * l.dw_sets), dim3(512), 0, s, (const float*)dgi, (const float*)dgh, d_x, d_hxs, d_y, d_masks, dwp, (int)N, M);
   HIP_OK(hipGetLastError());
@@ -441,5 +458,21 @@ int ac_gru_layer_backward(int32_t device_id, void* stream, int32_t N, int32_t T,
     HIP_OK(hipGetLastError());
   }
   return 0;
+}
+int ac_gru_layer_backward(int32_t device_id, void* stream, int32_t N, int32_t T, const float* d_g_out, const float* d_g_h_T, const float* d_x,
+                          const float* d_hxs, const float* d_masks, const float* d_w_ih, const float* d_w_hh, const float* d_gamma,
+                          const float* d_y, const float* d_saved, const float* d_stats, float* d_workspace, float* d_dx, float* d_dhxs,
+                          float* d_dw_ih, float* d_dw_hh, float* d_db_ih, float* d_db_hh, float* d_dgamma, float* d_dbeta) {
+  return gru_layer_backward("ac_gru_layer_backward", AC_PRODUCTS_FP32, device_id, stream, N, T, d_g_out, d_g_h_T, d_x, d_hxs, d_masks, d_w_ih,
+                            d_w_hh, d_gamma, d_y, d_saved, d_stats, d_workspace, d_dx, d_dhxs, d_dw_ih, d_dw_hh, d_db_ih, d_db_hh, d_dgamma, d_dbeta);
+}
+int ac_gru_layer_backward_p(int32_t device_id, void* stream, int32_t N, int32_t T, const float* d_g_out, const float* d_g_h_T,
+                            const float* d_x, const float* d_hxs, const float* d_masks, const float* d_w_ih, const float* d_w_hh,
+                            const float* d_gamma, const float* d_y, const float* d_saved, const float* d_stats, float* d_workspace,
+                            float* d_dx, float* d_dhxs, float* d_dw_ih, float* d_dw_hh, float* d_db_ih, float* d_db_hh, float* d_dgamma,
+                            float* d_dbeta, int32_t products) {
+  if (gru_products_ok("ac_gru_layer_backward_p", products)) return -1;
+  return gru_layer_backward("ac_gru_layer_backward_p", products, device_id, stream, N, T, d_g_out, d_g_h_T, d_x, d_hxs, d_masks, d_w_ih, d_w_hh,
+                            d_gamma, d_y, d_saved, d_stats, d_workspace, d_dx, d_dhxs, d_dw_ih, d_dw_hh, d_db_ih, d_db_hh, d_dgamma, d_dbeta);
 }
 }  // extern "C"

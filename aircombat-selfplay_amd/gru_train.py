@@ -7,6 +7,10 @@ synchronisation. The dense products around it (``x W_ihᵀ``, ``dx``, ``dW_ih``,
 
 ``use_device_gru(policy)`` swaps every GRULayer-shaped child of a policy for a ``DeviceGRULayer`` reusing the same ``gru`` and ``norm``
 submodules, so Parameter objects, optimiser state and checkpoints are unchanged.
+
+``products`` (everywhere it appears) is how the two recurrence kernels multiply by ``W_hh``: ``"fp32"``, the default, on the fp32
+matrix instruction; ``"bf16x3"`` with every value as three bf16 pieces and six piece products on the bf16 matrix instruction
+(csrc/gru_train_split.hpp), as exact as fp32 to the tests' bound and shorter per step. Nothing else depends on it.
 """
 import torch
 import torch.nn as nn
@@ -16,6 +20,14 @@ from .train_common import Launch, swap_children
 
 HID = 128
 SAVED = 4 * HID   # floats per (step, row) the forward keeps for the backward: r, z, n, W_hn h + b_hn
+PRODUCTS = {"fp32": 0, "bf16x3": 1}   # AC_PRODUCTS_FP32, AC_PRODUCTS_BF16X3 (include/aircombat.h)
+
+
+def products_code(products):
+    """The library's constant for ``products``; ValueError for anything but "fp32" / "bf16x3"."""
+    if not isinstance(products, str) or products not in PRODUCTS:
+        raise ValueError(f"products must be one of {', '.join(map(repr, PRODUCTS))}, not {products!r}")
+    return PRODUCTS[products]
 
 
 class DeviceGRUFunction(torch.autograd.Function):
@@ -26,7 +38,7 @@ class DeviceGRUFunction(torch.autograd.Function):
     always off and ``needs_input_grad`` ignores it)."""
 
     @staticmethod
-    def forward(ctx, x, hxs, masks, w_ih, w_hh, b_ih, b_hh, save):
+    def forward(ctx, x, hxs, masks, w_ih, w_hh, b_ih, b_hh, save, products=0):
         N = hxs.shape[0]
         T = x.shape[0] // N
         x, hxs, masks, w_hh, b_hh = x.contiguous(), hxs.contiguous(), masks.contiguous(), w_hh.contiguous(), b_hh.contiguous()
@@ -34,10 +46,11 @@ class DeviceGRUFunction(torch.autograd.Function):
         run = Launch(x)
         y, h_T = run.empty(T * N, HID), run.empty(N, HID)
         saved = run.empty(T * N, SAVED) if save else None
-        run("ac_gru_seq_forward", N, T, gi, hxs, masks, w_hh, b_hh, y, h_T, saved)
+        run("ac_gru_seq_forward_p", N, T, gi, hxs, masks, w_hh, b_hh, y, h_T, saved, products)
         if save:
             ctx.save_for_backward(x, hxs, masks, w_ih, w_hh, y, saved)
             ctx.shape = (N, T)
+            ctx.products = products
         ctx.set_materialize_grads(False)
         return y, h_T
 
@@ -51,7 +64,7 @@ class DeviceGRUFunction(torch.autograd.Function):
         dhxs = run.empty(N, HID) if need[1] else None
         dy = None if dy is None else dy.contiguous()
         dh_T = None if dh_T is None else dh_T.contiguous()
-        run("ac_gru_seq_backward", N, T, dy, dh_T, saved, y, hxs, masks, w_hh, dgi, dgh, dhxs)
+        run("ac_gru_seq_backward_p", N, T, dy, dh_T, saved, y, hxs, masks, w_hh, dgi, dgh, dhxs, ctx.products)
         dx = dgi @ w_ih if need[0] else None
         # the weight gradients as one batched GEMM over the steps (K = N each) and a sum over T: a single GEMM with K = T * N
         # accumulates in fp32 along the whole minibatch (measured 6.1e-6 relative against float64 at N = 4096, T = 60, torch's
@@ -64,13 +77,14 @@ class DeviceGRUFunction(torch.autograd.Function):
             dw_hh = torch.bmm(dgh.view(T, N, 3 * HID).transpose(1, 2), h_in).sum(0)
         db_ih = dgi.sum(0) if need[5] else None
         db_hh = dgh.sum(0) if need[6] else None
-        return dx, dhxs, None, dw_ih, dw_hh, db_ih, db_hh, None
+        return (dx, dhxs, None, dw_ih, dw_hh, db_ih, db_hh, None, None)[:len(need)]
 
 
-def gru_seq(x, hxs, masks, w_ih, w_hh, b_ih, b_hh):
+def gru_seq(x, hxs, masks, w_ih, w_hh, b_ih, b_hh, products="fp32"):
     """DeviceGRUFunction with its ``save`` decided here: grad mode on and some input requiring grad."""
+    code = products_code(products)
     save = torch.is_grad_enabled() and any(t.requires_grad for t in (x, hxs, w_ih, w_hh, b_ih, b_hh))
-    return DeviceGRUFunction.apply(x, hxs, masks, w_ih, w_hh, b_ih, b_hh, save)
+    return DeviceGRUFunction.apply(x, hxs, masks, w_ih, w_hh, b_ih, b_hh, save, code)
 
 
 def check_gru(gru, where="gru"):
@@ -103,10 +117,13 @@ def check_gru(gru, where="gru"):
 class DeviceGRULayer(nn.Module):
     """GRULayer(input_size, hidden_size, num_layers) of the reference with the recurrence on the device: children ``gru`` (nn.GRU) and
     ``norm`` (nn.LayerNorm), forward(x, hxs, masks) -> (norm(y), h_T [N, 1, 128]). ``x.size(0) == hxs.size(0)`` means T = 1, as there.
-    Given ``gru`` / ``norm``, those modules are used as they are (use_device_gru)."""
+    Given ``gru`` / ``norm``, those modules are used as they are (use_device_gru). ``products`` ("fp32" or "bf16x3", kept as
+    ``layer.products``) selects the recurrence kernels' product."""
 
-    def __init__(self, input_size=HID, hidden_size=HID, num_layers=1, gru=None, norm=None):
+    def __init__(self, input_size=HID, hidden_size=HID, num_layers=1, gru=None, norm=None, products="fp32"):
         super().__init__()
+        products_code(products)
+        self.products = products
         self._hidden_size = hidden_size
         self._num_layers = num_layers
         self.gru = gru if gru is not None else nn.GRU(input_size=input_size, hidden_size=hidden_size, num_layers=num_layers)
@@ -120,7 +137,7 @@ class DeviceGRULayer(nn.Module):
         if T * N != x.size(0):
             raise ValueError(f"x has {x.size(0)} rows, not a multiple of hxs' {N}")
         y, h_T = gru_seq(x, hxs.reshape(N, HID), masks.reshape(T * N).to(torch.float32), g.weight_ih_l0, g.weight_hh_l0, g.bias_ih_l0,
-                         g.bias_hh_l0)
+                         g.bias_hh_l0, self.products)
         return self.norm(y), h_T.view(N, 1, HID)
 
     @property
@@ -133,21 +150,24 @@ def check_one_layer(layer, where):
         raise UnsupportedPolicy(f"{where}: {layer._num_layers} layers (only 1)")
 
 
-def same_children(cls, layer):
+def same_children(cls, layer, products="fp32"):
     """``cls`` (DeviceGRULayer or a subclass) holding the very ``gru`` and ``norm`` of ``layer``."""
-    return cls(layer.gru.input_size, layer.gru.hidden_size, layer.gru.num_layers, gru=layer.gru, norm=layer.norm)
+    return cls(layer.gru.input_size, layer.gru.hidden_size, layer.gru.num_layers, gru=layer.gru, norm=layer.norm, products=products)
 
 
 def _gru_layer_shaped(m):
     return not isinstance(m, DeviceGRULayer) and isinstance(getattr(m, "gru", None), nn.GRU) and isinstance(getattr(m, "norm", None), nn.LayerNorm)
 
 
-def use_device_gru(module):
+def use_device_gru(module, products="fp32"):
     """Swap every GRULayer-shaped child (a module with an nn.GRU ``gru`` and an nn.LayerNorm ``norm``) of ``module`` for a
     DeviceGRULayer holding the same two submodules. ``module`` is an nn.Module (``policy.actor``, ``policy.critic``) or an object with
     ``actor`` / ``critic`` modules (the reference's PPO and MAPPO ``PPOPolicy``). Every layer is checked before any is swapped; an
-    unsupported one raises UnsupportedPolicy naming it. Returns the number of layers swapped."""
+    unsupported one raises UnsupportedPolicy naming it. Every new layer gets ``products``; one that is neither "fp32" nor "bf16x3" is a
+    ValueError before anything is looked at. Returns the number of layers swapped."""
+    products_code(products)
+
     def check(child, where):
         check_gru(child.gru, where + ".gru")
         check_one_layer(child, where)
-    return swap_children(module, _gru_layer_shaped, check, lambda child: same_children(DeviceGRULayer, child), "a GRULayer")
+    return swap_children(module, _gru_layer_shaped, check, lambda child: same_children(DeviceGRULayer, child, products), "a GRULayer")

@@ -490,6 +490,19 @@ int ac_gru_seq_forward(int32_t device_id, void* stream, int32_t N, int32_t T, co
 int ac_gru_seq_backward(int32_t device_id, void* stream, int32_t N, int32_t T, const float* d_dy, const float* d_dh_T, const float* d_saved,
                         const float* d_y, const float* d_hxs, const float* d_masks, const float* d_w_hh, float* d_dgi, float* d_dgh,
                         float* d_dhxs);
+/* How the two recurrence kernels multiply by W_hh ("The training GRU"). AC_PRODUCTS_FP32: the fp32 matrix instruction,
+ * what the calls above do. AC_PRODUCTS_BF16X3: every value as three bf16 pieces (their sum is the value exactly) and the six piece
+ * products of order <= 2 on the bf16 matrix instruction, accumulated in fp32: each product good to about 2^-23 of itself. W_hh is still
+ * the caller's fp32 tensor, read and split at every call. */
+#define AC_PRODUCTS_FP32 0
+#define AC_PRODUCTS_BF16X3 1
+/* the two calls above with `products`; AC_PRODUCTS_FP32 launches exactly what they launch. Also refused, before any launch: an
+ * unknown `products`. */
+int ac_gru_seq_forward_p(int32_t device_id, void* stream, int32_t N, int32_t T, const float* d_gi, const float* d_hxs, const float* d_masks,
+                         const float* d_w_hh, const float* d_b_hh, float* d_y, float* d_h_T, float* d_saved, int32_t products);
+int ac_gru_seq_backward_p(int32_t device_id, void* stream, int32_t N, int32_t T, const float* d_dy, const float* d_dh_T, const float* d_saved,
+                          const float* d_y, const float* d_hxs, const float* d_masks, const float* d_w_hh, float* d_dgi, float* d_dgh,
+                          float* d_dhxs, int32_t products);
 
 /* ---- the whole GRU layer of the PPO update on the device ("The whole GRU layer"): the reference's GRULayer, nn.GRU
  * 128 -> 128 of one layer then nn.LayerNorm(128), as one call per direction: the input product, the recurrence above, the LayerNorm and,
@@ -514,6 +527,18 @@ int ac_gru_layer_backward(int32_t device_id, void* stream, int32_t N, int32_t T,
                           const float* d_hxs, const float* d_masks, const float* d_w_ih, const float* d_w_hh, const float* d_gamma,
                           const float* d_y, const float* d_saved, const float* d_stats, float* d_workspace, float* d_dx, float* d_dhxs,
                           float* d_dw_ih, float* d_dw_hh, float* d_db_ih, float* d_db_hh, float* d_dgamma, float* d_dbeta);
+/* the two calls above with `products` (AC_PRODUCTS_FP32 / AC_PRODUCTS_BF16X3, above): it selects the recurrence kernel alone; the
+ * input product, the LayerNorm, the weight and input gradients and the workspace are the same. AC_PRODUCTS_FP32 launches exactly what
+ * the calls above launch; an unknown `products` is refused before any launch. */
+int ac_gru_layer_forward_p(int32_t device_id, void* stream, int32_t N, int32_t T, const float* d_x, const float* d_hxs, const float* d_masks,
+                           const float* d_w_ih, const float* d_w_hh, const float* d_b_ih, const float* d_b_hh, const float* d_gamma,
+                           const float* d_beta, float eps, float* d_workspace, float* d_out, float* d_h_T, float* d_y, float* d_saved,
+                           float* d_stats, int32_t products);
+int ac_gru_layer_backward_p(int32_t device_id, void* stream, int32_t N, int32_t T, const float* d_g_out, const float* d_g_h_T,
+                            const float* d_x, const float* d_hxs, const float* d_masks, const float* d_w_ih, const float* d_w_hh,
+                            const float* d_gamma, const float* d_y, const float* d_saved, const float* d_stats, float* d_workspace,
+                            float* d_dx, float* d_dhxs, float* d_dw_ih, float* d_dw_hh, float* d_db_ih, float* d_db_hh, float* d_dgamma,
+                            float* d_dbeta, int32_t products);
 /* the kernels' constants, for tests that size themselves: 0 rows per tile (every kernel), then the workgroups at most of 1 the input
  * product, 2 the LayerNorm forward, 3 the LayerNorm backward, 4 the weight gradients (per gradient), 5 the input gradient; -1 otherwise */
 int32_t ac_gru_layer_constant(int32_t which);
