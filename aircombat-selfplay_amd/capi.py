@@ -344,6 +344,9 @@ SIGNATURES = {
     "ac_gru_seq_backward_p": (C.c_int, [C.c_int32, _p, C.c_int32, C.c_int32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, C.c_int32]),
     "ac_gru_layer_forward_p": (C.c_int, [C.c_int32, _p, C.c_int32, C.c_int32] + [_p] * 9 + [C.c_float] + [_p] * 6 + [C.c_int32]),
     "ac_gru_layer_backward_p": (C.c_int, [C.c_int32, _p, C.c_int32, C.c_int32] + [_p] * 20 + [C.c_int32]),
+    # the two layer calls above with `dense_products` (the same two constants) after `products`
+    "ac_gru_layer_forward_pd": (C.c_int, [C.c_int32, _p, C.c_int32, C.c_int32] + [_p] * 9 + [C.c_float] + [_p] * 6 + [C.c_int32, C.c_int32]),
+    "ac_gru_layer_backward_pd": (C.c_int, [C.c_int32, _p, C.c_int32, C.c_int32] + [_p] * 20 + [C.c_int32, C.c_int32]),
     "ac_mlp_block_workspace_floats": (C.c_int64, [C.c_int32, C.c_int32]),
     "ac_mlp_block_forward": (C.c_int, [C.c_int32, _p, C.c_int32, C.c_int32, C.c_float, _p, _p, _p, _p, _p, _p, _p]),
     "ac_mlp_block_backward": (C.c_int, [C.c_int32, _p, C.c_int32, C.c_int32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),

@@ -21,6 +21,9 @@
 // Parameter-gradient sums: every workgroup writes its set of partial sums to the workspace and gru_sum_partials adds the sets in an
 // order fixed by their number alone (eight interleaved running sums, then a tree). A workgroup's running sum covers its own rows only
 // (1/128 of them in gru_dw, 1/4096 per wave in gru_ln_bwd). No floating-point atomics: results are bit-identical from run to run.
+//
+// gru_layer_train_split.hpp has a second form of the three products (gi, dw, dx) on the bf16 matrix path; the host code below launches
+// either through grul::Dense.
 #pragma once
 
 #include "mlp_train.hpp"
@@ -357,6 +360,13 @@ inline Layout layout(int M) {
   l.total = l.lnp + (int64_t)l.ln_sets * LN_NEL;
   return l;
 }
+// the three dense products' kernels: this file's, or those of gru_layer_train_split.hpp
+struct Dense {
+  void (*gi)(const float*, const float*, const float*, float*, int);
+  void (*dw)(const float*, const float*, const float*, const float*, const float*, const float*, float*, int, int);
+  void (*dx)(const float*, const float*, float*, int);
+};
+inline Dense dense_fp32() { return {gru_gi_fwd, gru_dw, gru_dx}; }
 }  // namespace grul
 
 // ------------------------------------------------------------------------------------------------ C ABI (include/aircombat.h)
@@ -380,8 +390,9 @@ int32_t ac_gru_layer_constant(int32_t which) {
   }
 }
 
-// `who` names the entry in its refusals; `products` (checked by the caller) selects the recurrence kernel alone
-static int gru_layer_forward(const std::string& who, int32_t products, int32_t device_id, void* stream, int32_t N, int32_t T, const float* d_x,
+// `who` names the entry in its refusals; `products` (checked by the caller) selects the recurrence kernel alone, `dense` the three
+// dense products' kernels
+static int gru_layer_forward(const std::string& who, int32_t products, const grul::Dense& dense, int32_t device_id, void* stream, int32_t N, int32_t T, const float* d_x,
                              const float* d_hxs, const float* d_masks, const float* d_w_ih, const float* d_w_hh, const float* d_b_ih,
                              const float* d_b_hh, const float* d_gamma, const float* d_beta, float eps, float* d_workspace, float* d_out,
                              float* d_h_T, float* d_y, float* d_saved, float* d_stats) {
@@ -394,7 +405,7 @@ static int gru_layer_forward(const std::string& who, int32_t products, int32_t d
   HIP_OK(hipSetDevice(device_id));
   const int M = N * T;
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(grul::gru_gi_fwd, dim3(trn::capped_tiles(M, grul::RT, grul::GI_WGS)), dim3(512), 0, s, d_x, d_w_ih, d_b_ih, d_workspace, M);
+  hipLaunchKernelGGL(dense.gi, dim3(trn::capped_tiles(M, grul::RT, grul::GI_WGS)), dim3(512), 0, s, d_x, d_w_ih, d_b_ih, d_workspace, M);
   HIP_OK(hipGetLastError());
   hipLaunchKernelGGL(products == AC_PRODUCTS_BF16X3 ? grus::gru_seq_fwd_b3 : grut::gru_seq_fwd, dim3(trn::tiles(N, grut::RT)), dim3(512), 0, s,
                      (const float*)d_workspace, d_hxs, d_masks, d_w_hh, d_b_hh, d_y, d_h_T, d_saved, (int)N, (int)T);
@@ -407,7 +418,7 @@ int ac_gru_layer_forward(int32_t device_id, void* stream, int32_t N, int32_t T, 
                          const float* d_w_ih, const float* d_w_hh, const float* d_b_ih, const float* d_b_hh, const float* d_gamma,
                          const float* d_beta, float eps, float* d_workspace, float* d_out, float* d_h_T, float* d_y, float* d_saved,
                          float* d_stats) {
-  return gru_layer_forward("ac_gru_layer_forward", AC_PRODUCTS_FP32, device_id, stream, N, T, d_x, d_hxs, d_masks, d_w_ih, d_w_hh, d_b_ih, d_b_hh,
+  return gru_layer_forward("ac_gru_layer_forward", AC_PRODUCTS_FP32, grul::dense_fp32(), device_id, stream, N, T, d_x, d_hxs, d_masks, d_w_ih, d_w_hh, d_b_ih, d_b_hh,
                            d_gamma, d_beta, eps, d_workspace, d_out, d_h_T, d_y, d_saved, d_stats);
 }
 int ac_gru_layer_forward_p(int32_t device_id, void* stream, int32_t N, int32_t T, const float* d_x, const float* d_hxs, const float* d_masks,
@@ -415,11 +426,11 @@ int ac_gru_layer_forward_p(int32_t device_id, void* stream, int32_t N, int32_t T
                            const float* d_beta, float eps, float* d_workspace, float* d_out, float* d_h_T, float* d_y, float* d_saved,
                            float* d_stats, int32_t products) {
   if (gru_products_ok("ac_gru_layer_forward_p", products)) return -1;
-  return gru_layer_forward("ac_gru_layer_forward_p", products, device_id, stream, N, T, d_x, d_hxs, d_masks, d_w_ih, d_w_hh, d_b_ih, d_b_hh,
+  return gru_layer_forward("ac_gru_layer_forward_p", products, grul::dense_fp32(), device_id, stream, N, T, d_x, d_hxs, d_masks, d_w_ih, d_w_hh, d_b_ih, d_b_hh,
                            d_gamma, d_beta, eps, d_workspace, d_out, d_h_T, d_y, d_saved, d_stats);
 }
 
-static int gru_layer_backward(const std::string& who, int32_t products, int32_t device_id, void* stream, int32_t N, int32_t T, const float* d_g_out,
+static int gru_layer_backward(const std::string& who, int32_t products, const grul::Dense& dense, int32_t device_id, void* stream, int32_t N, int32_t T, const float* d_g_out,
                               const float* d_g_h_T, const float* d_x, const float* d_hxs, const float* d_masks, const float* d_w_ih,
                               const float* d_w_hh, const float* d_gamma, const float* d_y, const float* d_saved, const float* d_stats,
                               float* d_workspace, float* d_dx, float* d_dhxs, float* d_dw_ih, float* d_dw_hh, float* d_db_ih, float* d_db_hh,
@@ -448,13 +459,13 @@ static int gru_layer_backward(const std::string& who, int32_t products, int32_t 
   hipLaunchKernelGGL(products == AC_PRODUCTS_BF16X3 ? grus::gru_seq_bwd_b3 : grut::gru_seq_bwd, dim3(trn::tiles(N, grut::RT)), dim3(512), 0, s,
                      d_g_out ? (const float*)dy : nullptr, d_g_h_T, d_saved, d_y, d_hxs, d_masks, d_w_hh, dgi, dgh, d_dhxs, (int)N, (int)T);
   HIP_OK(hipGetLastError());
-  hipLaunchKernelGGL(grul::gru_dw, dim3(2 * l.dw_sets), dim3(512), 0, s, (const float*)dgi, (const float*)dgh, d_x, d_hxs, d_y, d_masks, dwp, (int)N, M);
+  hipLaunchKernelGGL(dense.dw, dim3(2 * l.dw_sets), dim3(512), 0, s, (const float*)dgi, (const float*)dgh, d_x, d_hxs, d_y, d_masks, dwp, (int)N, M);
   HIP_OK(hipGetLastError());
   hipLaunchKernelGGL(grul::gru_sum_partials, dim3((grul::DW_NEL + 255) / 256, 2), dim3(256), 0, s, (const float*)dwp, l.dw_sets, grul::DW_NEL,
                      grul::G * grul::H, d_dw_ih, d_db_ih, d_dw_hh, d_db_hh);
   HIP_OK(hipGetLastError());
   if (d_dx) {
-    hipLaunchKernelGGL(grul::gru_dx, dim3(trn::capped_tiles(M, grul::RT, grul::DX_WGS)), dim3(512), 0, s, (const float*)dgi, d_w_ih, d_dx, M);
+    hipLaunchKernelGGL(dense.dx, dim3(trn::capped_tiles(M, grul::RT, grul::DX_WGS)), dim3(512), 0, s, (const float*)dgi, d_w_ih, d_dx, M);
     HIP_OK(hipGetLastError());
   }
   return 0;
@@ -463,7 +474,7 @@ int ac_gru_layer_backward(int32_t device_id, void* stream, int32_t N, int32_t T,
                           const float* d_hxs, const float* d_masks, const float* d_w_ih, const float* d_w_hh, const float* d_gamma,
                           const float* d_y, const float* d_saved, const float* d_stats, float* d_workspace, float* d_dx, float* d_dhxs,
                           float* d_dw_ih, float* d_dw_hh, float* d_db_ih, float* d_db_hh, float* d_dgamma, float* d_dbeta) {
-  return gru_layer_backward("ac_gru_layer_backward", AC_PRODUCTS_FP32, device_id, stream, N, T, d_g_out, d_g_h_T, d_x, d_hxs, d_masks, d_w_ih,
+  return gru_layer_backward("ac_gru_layer_backward", AC_PRODUCTS_FP32, grul::dense_fp32(), device_id, stream, N, T, d_g_out, d_g_h_T, d_x, d_hxs, d_masks, d_w_ih,
                             d_w_hh, d_gamma, d_y, d_saved, d_stats, d_workspace, d_dx, d_dhxs, d_dw_ih, d_dw_hh, d_db_ih, d_db_hh, d_dgamma, d_dbeta);
 }
 int ac_gru_layer_backward_p(int32_t device_id, void* stream, int32_t N, int32_t T, const float* d_g_out, const float* d_g_h_T,
@@ -472,7 +483,7 @@ int ac_gru_layer_backward_p(int32_t device_id, void* stream, int32_t N, int32_t 
                             float* d_dx, float* d_dhxs, float* d_dw_ih, float* d_dw_hh, float* d_db_ih, float* d_db_hh, float* d_dgamma,
                             float* d_dbeta, int32_t products) {
   if (gru_products_ok("ac_gru_layer_backward_p", products)) return -1;
-  return gru_layer_backward("ac_gru_layer_backward_p", products, device_id, stream, N, T, d_g_out, d_g_h_T, d_x, d_hxs, d_masks, d_w_ih, d_w_hh,
+  return gru_layer_backward("ac_gru_layer_backward_p", products, grul::dense_fp32(), device_id, stream, N, T, d_g_out, d_g_h_T, d_x, d_hxs, d_masks, d_w_ih, d_w_hh,
                             d_gamma, d_y, d_saved, d_stats, d_workspace, d_dx, d_dhxs, d_dw_ih, d_dw_hh, d_db_ih, d_db_hh, d_dgamma, d_dbeta);
 }
 }  // extern "C"

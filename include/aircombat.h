@@ -539,6 +539,21 @@ int ac_gru_layer_backward_p(int32_t device_id, void* stream, int32_t N, int32_t 
                             const float* d_gamma, const float* d_y, const float* d_saved, const float* d_stats, float* d_workspace,
                             float* d_dx, float* d_dhxs, float* d_dw_ih, float* d_dw_hh, float* d_db_ih, float* d_db_hh, float* d_dgamma,
                             float* d_dbeta, int32_t products);
+/* the two `_p` calls with `dense_products` (AC_PRODUCTS_FP32 / AC_PRODUCTS_BF16X3) as well: it selects, independently of `products`,
+ * how the layer's three dense products are formed -- gi = x W_ihᵀ, dx = dgi W_ih and the weight gradients dW_ih, dW_hh. AC_PRODUCTS_BF16X3:
+ * every value as three bf16 pieces and the six piece products of order <= 2 on the bf16 matrix instruction, accumulated in fp32; W_ih
+ * is still the caller's fp32 tensor, read and split at every call; the bias gradients stay fp32 sums. Arguments, outputs, the
+ * workspace and its size are the same; results are bit-identical from run to run. AC_PRODUCTS_FP32 launches exactly what the `_p`
+ * calls launch. Refused as there, and an unknown `dense_products` before any launch. */
+int ac_gru_layer_forward_pd(int32_t device_id, void* stream, int32_t N, int32_t T, const float* d_x, const float* d_hxs, const float* d_masks,
+                            const float* d_w_ih, const float* d_w_hh, const float* d_b_ih, const float* d_b_hh, const float* d_gamma,
+                            const float* d_beta, float eps, float* d_workspace, float* d_out, float* d_h_T, float* d_y, float* d_saved,
+                            float* d_stats, int32_t products, int32_t dense_products);
+int ac_gru_layer_backward_pd(int32_t device_id, void* stream, int32_t N, int32_t T, const float* d_g_out, const float* d_g_h_T,
+                             const float* d_x, const float* d_hxs, const float* d_masks, const float* d_w_ih, const float* d_w_hh,
+                             const float* d_gamma, const float* d_y, const float* d_saved, const float* d_stats, float* d_workspace,
+                             float* d_dx, float* d_dhxs, float* d_dw_ih, float* d_dw_hh, float* d_db_ih, float* d_db_hh, float* d_dgamma,
+                             float* d_dbeta, int32_t products, int32_t dense_products);
 /* the kernels' constants, for tests that size themselves: 0 rows per tile (every kernel), then the workgroups at most of 1 the input
  * product, 2 the LayerNorm forward, 3 the LayerNorm backward, 4 the weight gradients (per gradient), 5 the input gradient; -1 otherwise */
 int32_t ac_gru_layer_constant(int32_t which);
