@@ -350,6 +350,9 @@ SIGNATURES = {
     "ac_mlp_block_workspace_floats": (C.c_int64, [C.c_int32, C.c_int32]),
     "ac_mlp_block_forward": (C.c_int, [C.c_int32, _p, C.c_int32, C.c_int32, C.c_float, _p, _p, _p, _p, _p, _p, _p]),
     "ac_mlp_block_backward": (C.c_int, [C.c_int32, _p, C.c_int32, C.c_int32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "ac_mlp_block_forward_p": (C.c_int, [C.c_int32, _p, C.c_int32, C.c_int32, C.c_float, _p, _p, _p, _p, _p, _p, _p, C.c_int32]),
+    "ac_mlp_block_backward_p": (C.c_int, [C.c_int32, _p, C.c_int32, C.c_int32] + [_p] * 12 + [C.c_int32]),
+    "ac_mlp_block_constant": (C.c_int32, [C.c_int32]),
     "ac_act_eval_workspace_floats": (C.c_int64, [C.POINTER(AcActHeads), C.c_int32]),
     "ac_act_eval_forward": (C.c_int, [C.c_int32, _p, C.POINTER(AcActHeads), C.c_int32, _p, _p, _p, _p, _p, _p, _p, _p]),
     "ac_act_eval_backward": (C.c_int, [C.c_int32, _p, C.POINTER(AcActHeads), C.c_int32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),

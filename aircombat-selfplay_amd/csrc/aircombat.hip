@@ -3030,6 +3030,7 @@ int ac_get_missile_target(ac_env_t* h, int32_t env, int32_t agent, int32_t k, in
 #include "gru_train.hpp"
 #include "gru_train_split.hpp"
 #include "mlp_train.hpp"
+#include "mlp_train_split.hpp"
 #include "act_train.hpp"
 #include "ppo_update.hpp"
 #include "collect_common.hpp"

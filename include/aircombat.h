@@ -573,6 +573,23 @@ int ac_mlp_block_forward(int32_t device_id, void* stream, int32_t M, int32_t K, 
 int ac_mlp_block_backward(int32_t device_id, void* stream, int32_t M, int32_t K, const float* d_dy, const float* d_x, const float* d_w,
                           const float* d_b, const float* d_gamma, const float* d_stats, float* d_workspace, float* d_dx, float* d_dw,
                           float* d_db, float* d_dgamma, float* d_dbeta);
+/* the two calls above with `products` (AC_PRODUCTS_FP32 / AC_PRODUCTS_BF16X3, above). AC_PRODUCTS_BF16X3 forms the block's three
+ * products -- z = x Wᵀ (in the forward and again in the backward's recomputation, by one shared function, so the ReLU mask is the
+ * same bit for bit), dx = dz W and dW = dzᵀ x -- from three bf16 pieces per value and the six piece products of order <= 2 on the bf16
+ * matrix instruction, accumulated in fp32; W is still the caller's fp32 tensor, read and split at every call; the bias, the ReLU, the
+ * LayerNorm and db, dgamma, dbeta stay fp32. Arguments, outputs, the workspace and its size are the same; results are bit-identical
+ * from run to run. A forward and its backward must be given the same `products`. Where the padded K has no split kernel
+ * (ac_mlp_block_constant(3)) AC_PRODUCTS_BF16X3 launches the fp32 kernels; AC_PRODUCTS_FP32 launches exactly what the calls above
+ * launch. Refused as there, and an unknown `products` before any launch. */
+int ac_mlp_block_forward_p(int32_t device_id, void* stream, int32_t M, int32_t K, float eps, const float* d_x, const float* d_w,
+                           const float* d_b, const float* d_gamma, const float* d_beta, float* d_y, float* d_stats, int32_t products);
+int ac_mlp_block_backward_p(int32_t device_id, void* stream, int32_t M, int32_t K, const float* d_dy, const float* d_x, const float* d_w,
+                            const float* d_b, const float* d_gamma, const float* d_stats, float* d_workspace, float* d_dx, float* d_dw,
+                            float* d_db, float* d_dgamma, float* d_dbeta, int32_t products);
+/* the kernels' constants, for tests that size themselves: 0 rows per tile, 1 the forward's workgroups at most, 2 the backward's (also
+ * its partial sets at most), 3 a bitmask of the padded K (32, 64, 128, 256; K <= 32 pads to 32 in the split form) for which
+ * AC_PRODUCTS_BF16X3 runs a split kernel; -1 otherwise */
+int32_t ac_mlp_block_constant(int32_t which);
 
 /* ---- the PPO update's action heads on the device ("The training action heads"): ACTLayer.evaluate_actions of the reference
  * for n_cat Categorical heads (logits_net: W_h [nvec[h], 128], b_h [nvec[h]]) and, with n_shoot_cols 1 or 4, ONE BetaShootBernoulli head
