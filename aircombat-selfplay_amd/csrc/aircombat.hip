@@ -3027,6 +3027,7 @@ int ac_get_missile_target(ac_env_t* h, int32_t env, int32_t agent, int32_t k, in
 #include "policy_host.hpp"
 #include "policy_pool.hpp"
 #include "train_common.hpp"
+#include "bf16x3.hpp"
 #include "gru_train.hpp"
 #include "gru_train_split.hpp"
 #include "mlp_train.hpp"

@@ -425,7 +425,7 @@ int ac_gru_layer_forward_p(int32_t device_id, void* stream, int32_t N, int32_t T
                            const float* d_w_ih, const float* d_w_hh, const float* d_b_ih, const float* d_b_hh, const float* d_gamma,
                            const float* d_beta, float eps, float* d_workspace, float* d_out, float* d_h_T, float* d_y, float* d_saved,
                            float* d_stats, int32_t products) {
-  if (gru_products_ok("ac_gru_layer_forward_p", products)) return -1;
+  if (trn::products_ok("ac_gru_layer_forward_p", "products", products)) return -1;
   return gru_layer_forward("ac_gru_layer_forward_p", products, grul::dense_fp32(), device_id, stream, N, T, d_x, d_hxs, d_masks, d_w_ih, d_w_hh, d_b_ih, d_b_hh,
                            d_gamma, d_beta, eps, d_workspace, d_out, d_h_T, d_y, d_saved, d_stats);
 }
@@ -482,7 +482,7 @@ int ac_gru_layer_backward_p(int32_t device_id, void* stream, int32_t N, int32_t 
                             const float* d_gamma, const float* d_y, const float* d_saved, const float* d_stats, float* d_workspace,
                             float* d_dx, float* d_dhxs, float* d_dw_ih, float* d_dw_hh, float* d_db_ih, float* d_db_hh, float* d_dgamma,
                             float* d_dbeta, int32_t products) {
-  if (gru_products_ok("ac_gru_layer_backward_p", products)) return -1;
+  if (trn::products_ok("ac_gru_layer_backward_p", "products", products)) return -1;
   return gru_layer_backward("ac_gru_layer_backward_p", products, grul::dense_fp32(), device_id, stream, N, T, d_g_out, d_g_h_T, d_x, d_hxs, d_masks, d_w_ih, d_w_hh,
                             d_gamma, d_y, d_saved, d_stats, d_workspace, d_dx, d_dhxs, d_dw_ih, d_dw_hh, d_db_ih, d_db_hh, d_dgamma, d_dbeta);
 }

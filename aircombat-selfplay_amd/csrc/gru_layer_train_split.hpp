@@ -4,25 +4,18 @@
 // places: T-major rows, 32-row tiles, a persistent loop with the next tile asked for into registers before the current tile's
 // products, and for gru_dw_b3 the same partial sets in the same layout, so gru_sum_partials, grul::layout and the workspace are shared.
 //
-// The product is gru_train_split.hpp's: every fp32 value is three bf16 pieces (ctls::split3_pair, exact), a product keeps the six
-// terms b_i b_j with i + j <= 2 on v_mfma_f32_16x16x32_bf16 (ctl8::mf<3>), smallest first within a k-step. W_ih is read from the
-// caller's fp32 tensor at every call and split in registers once per workgroup (36 uint4 = 144 VGPRs in gi and dx); nothing is kept
-// between calls. The streamed operand is split once per tile by the thread that stores it, into three bf16 planes in LDS, and read
-// back with ds_read_b128.
+// The product is bf16x3.hpp's. W_ih is split once per workgroup (36 uint4 = 144 VGPRs in gi and dx); the streamed operand is split
+// once per tile by the thread that stores it.
 //
 //   gi   x tile [32][128 + 8] per plane (272 B rows), two buffers: one barrier per tile. A wave's 2 x 3 result tiles are six
 //        independent accumulators, each one chain over the 4 k-steps (24 terms), as gru_seq_fwd_b3.
 //   dx   dgi tile [32][384 + 8] per plane (784 B rows), two buffers (150 528 B of the CU's 160 KB; the 144 weight registers leave
-//        room for one workgroup per CU whatever the LDS): one barrier per tile. Three accumulation chains per result, two terms of
-//        every k-step each, added smallest first, as gru_seq_bwd_b3; one 16-row half of the tile after the other (both at once
-//        spilled two registers).
-//   dw   the sum runs over rows, so both operands want eight rows of one column per lane. The k slot 8 q + e of the instruction is
-//        row 16 (e / 4) + 4 q + e % 4 of the tile: then the gate gradients are the A operand straight from memory in the very lanes
-//        gru_dw loads them into (rows 16 mt + 4 q + i, gate column 48 w + 16 j + n), split in registers, and db is the same fp32
-//        tree of the unsplit values. x (or h_in, rebuilt while the tile is loaded; a masked row is +-0 and splits to three zero
-//        pieces) is the B operand from a transposed image [column][k slot] (80 B per column: the 16 columns of a lane quarter cover
-//        the 64 banks once), written as packed row pairs by threads that load two adjacent rows each; two buffers, one barrier per
-//        tile.
+//        room for one workgroup per CU whatever the LDS): one barrier per tile. Three chains per result (chains_pairs), as
+//        gru_seq_bwd_b3; one 16-row half of the tile after the other (both at once spilled two registers).
+//   dw   the sum runs over rows (k slots): the gate gradients are the A operand straight from memory in the very lanes gru_dw loads
+//        them into (rows 16 mt + 4 q + i, gate column 48 w + 16 j + n), split in registers, and db is the same fp32 tree of the
+//        unsplit values. x (or h_in, rebuilt while the tile is loaded) is the B operand from the transposed image, written as packed
+//        row pairs by threads that load two adjacent rows each; two buffers, one barrier per tile.
 //
 // dW keeps one fp32 accumulator per result for all six terms (96 registers), not b0 b0 in one of its own: 192 accumulator registers
 // do not fit beside the operands in the 256 a wave of a 512-thread workgroup has, and the measurement does not ask for it. In the
@@ -35,20 +28,9 @@
 
 namespace grls {
 using grul::floatx4; using grul::H; using grul::G; using grul::RT;
-using grus::mf; using grus::split8;
 constexpr int KX = H + 8;    // bf16 per plane row of an x tile
 constexpr int KG = G + 8;    // of a dgi tile
 constexpr int KR = RT + 8;   // of the transposed x image of gru_dw_b3: k slots per column
-constexpr int TI[6] = {2, 1, 0, 1, 0, 0}, TJ[6] = {0, 1, 2, 0, 1, 0};   // the six terms (A piece, B piece), smallest first
-
-// four adjacent values of a row -> 8 bytes in each plane (`at` 8-byte aligned, plane stride `pln` in bf16)
-__device__ __forceinline__ void store4(unsigned short* at, int pln, float a, float b, float c, float d) {
-  unsigned lo[3], hi[3];
-  ctls::split3_pair(a, b, lo[0], lo[1], lo[2]);
-  ctls::split3_pair(c, d, hi[0], hi[1], hi[2]);
-#pragma unroll
-  for (int p = 0; p < 3; ++p) *reinterpret_cast<uint2*>(at + p * pln) = make_uint2(lo[p], hi[p]);
-}
 
 // gi [M, 384] = x [M, 128] W_ihᵀ + b_ih. Wave w owns gate columns 48 w .. 48 w + 47 as gru_gi_fwd: B[j][s] = the pieces of
 // W_ih[48 w + 16 j + n][k = 32 s + 8 q + e].
@@ -62,13 +44,7 @@ __global__ __launch_bounds__(512) void gru_gi_fwd_b3(const float* __restrict__ x
   float bias[3];
 #pragma unroll
   for (int j = 0; j < 3; ++j) {
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-      const float* p = wih + (size_t)(c0 + 16 * j) * H + 32 * s + 8 * q;
-      const float4 v0 = *reinterpret_cast<const float4*>(p), v1 = *reinterpret_cast<const float4*>(p + 4);
-      const float v[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
-      split8(v, B[j][s][0], B[j][s][1], B[j][s][2]);
-    }
+    b3::row_slice<4>(B[j], wih + (size_t)(c0 + 16 * j) * H, q);
     bias[j] = bih[c0 + 16 * j];
   }
   const int ntiles = (M + RT - 1) / RT;
@@ -80,7 +56,7 @@ __global__ __launch_bounds__(512) void gru_gi_fwd_b3(const float* __restrict__ x
 #pragma unroll
     for (int j = 0; j < RT * H / 2048; ++j) {
       const int f = tid + 512 * j;
-      store4(img + (f / (H / 4)) * KX + 4 * (f % (H / 4)), PLN, pre[4 * j], pre[4 * j + 1], pre[4 * j + 2], pre[4 * j + 3]);
+      b3::store_row(img + (f / (H / 4)) * KX + 4 * (f % (H / 4)), PLN, pre + 4 * j);
     }
     __syncthreads();   // the only one per tile: the next store goes to the other buffer, the one after it follows the next barrier
     const int next = tile + gridDim.x;
@@ -95,16 +71,14 @@ __global__ __launch_bounds__(512) void gru_gi_fwd_b3(const float* __restrict__ x
     for (int s = 0; s < 4; ++s) {
       uint4 A[2][3];
 #pragma unroll
-      for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-        for (int p = 0; p < 3; ++p) A[mt][p] = *reinterpret_cast<const uint4*>(arow + p * PLN + 16 * mt * KX + 32 * s);
-#pragma unroll
-      for (int k = 0; k < 6; ++k)
+      for (int mt = 0; mt < 2; ++mt) b3::read3(A[mt], arow + 16 * mt * KX + 32 * s, PLN);
+      b3::one_chain([&](int ti, int tj) {
 #pragma unroll
         for (int j = 0; j < 3; ++j) {
-          acc[0][j] = mf(A[0][TI[k]], B[j][s][TJ[k]], acc[0][j]);
-          acc[1][j] = mf(A[1][TI[k]], B[j][s][TJ[k]], acc[1][j]);
+          acc[0][j] = b3::mf(A[0][ti], B[j][s][tj], acc[0][j]);
+          acc[1][j] = b3::mf(A[1][ti], B[j][s][tj], acc[1][j]);
         }
+      });
     }
 #pragma unroll
     for (int mt = 0; mt < 2; ++mt)
@@ -128,13 +102,7 @@ __global__ __launch_bounds__(512) void gru_dx_b3(const float* __restrict__ dgi, 
   const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63, n = lane & 15, q = lane >> 4;
   const int u = 16 * wv + n;
   uint4 B[12][3];
-#pragma unroll
-  for (int s = 0; s < 12; ++s) {
-    float v[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) v[e] = wih[(size_t)(32 * s + 8 * q + e) * H + u];
-    split8(v, B[s][0], B[s][1], B[s][2]);
-  }
+  b3::col_slice<12>(B, wih, H, u, q);
   const int ntiles = (M + RT - 1) / RT;
   float pre[RT * G / 512];
   int tile = blockIdx.x, buf = 0;
@@ -144,33 +112,27 @@ __global__ __launch_bounds__(512) void gru_dx_b3(const float* __restrict__ dgi, 
 #pragma unroll
     for (int j = 0; j < RT * G / 2048; ++j) {
       const int f = tid + 512 * j;
-      store4(img + (f / (G / 4)) * KG + 4 * (f % (G / 4)), PLN, pre[4 * j], pre[4 * j + 1], pre[4 * j + 2], pre[4 * j + 3]);
+      b3::store_row(img + (f / (G / 4)) * KG + 4 * (f % (G / 4)), PLN, pre + 4 * j);
     }
     __syncthreads();   // the only one per tile: the next store goes to the other buffer, the one after it follows the next barrier
     const int next = tile + gridDim.x;
     if (next < ntiles) grul::load_rows<G>(pre, dgi, M, next * RT, tid);
-    // three accumulation chains per result, two terms of every k-step each, added smallest first; one 16-row half of the tile after
-    // the other (both at once do not fit the registers beside the weights and the tile on its way)
+    // three accumulation chains per result; one 16-row half of the tile after the other (both at once do not fit the registers
+    // beside the weights and the tile on its way)
 #pragma unroll
     for (int mt = 0; mt < 2; ++mt) {
-      floatx4 c0 = {0.0f, 0.0f, 0.0f, 0.0f}, c1 = c0, c2 = c0;
+      floatx4 c[3] = {};
       const unsigned short* arow = img + (16 * mt + n) * KG + 8 * q;
 #pragma unroll
       for (int s = 0; s < 12; ++s) {
         uint4 A[3];
-#pragma unroll
-        for (int p = 0; p < 3; ++p) A[p] = *reinterpret_cast<const uint4*>(arow + p * PLN + 32 * s);
-        c0 = mf(A[2], B[s][0], c0);
-        c1 = mf(A[1], B[s][1], c1);
-        c2 = mf(A[0], B[s][2], c2);
-        c0 = mf(A[1], B[s][0], c0);
-        c1 = mf(A[0], B[s][1], c1);
-        c2 = mf(A[0], B[s][0], c2);
+        b3::read3(A, arow + 32 * s, PLN);
+        b3::chains_pairs(c, A, B[s]);
       }
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const int row = tile * RT + 16 * mt + 4 * q + i;
-        if (row < M) dx[(size_t)row * H + u] = (c0[i] + c1[i]) + c2[i];
+        if (row < M) dx[(size_t)row * H + u] = b3::chain_sum(c, i);
       }
     }
   }
@@ -187,9 +149,8 @@ __global__ __launch_bounds__(512) void gru_dw_b3(const float* __restrict__ dgi, 
   const int hh = blockIdx.x & 1, wg = blockIdx.x >> 1, nwg = gridDim.x >> 1;
   const float* __restrict__ D = hh ? dgh : dgi;
   const int c0 = 48 * wv + n;
-  // this thread's share of the B operand's tile: rows 2 rp and 2 rp + 1, columns 4 cq .. 4 cq + 3; their k slots are ks and ks + 1
+  // this thread's share of the B operand's tile: rows 2 rp and 2 rp + 1, columns 4 cq .. 4 cq + 3
   const int rp = tid & 15, cq = tid >> 4;
-  const int ks = 8 * ((rp >> 1) & 3) + 4 * (rp >> 3) + 2 * (rp & 1);
   floatx4 acc[3][8];   // dW[gate row 48 w + 16 j + 4 q + i][column 16 c + n], summed over every row this workgroup walks
 #pragma unroll
   for (int j = 0; j < 3; ++j)
@@ -197,7 +158,7 @@ __global__ __launch_bounds__(512) void gru_dw_b3(const float* __restrict__ dgi, 
     for (int c = 0; c < 8; ++c) acc[j][c] = floatx4{0.0f, 0.0f, 0.0f, 0.0f};
   float dbias[3] = {0.0f, 0.0f, 0.0f};
   const int ntiles = (M + RT - 1) / RT;
-  float pd[2][4][3], px[2][4];
+  float pd[3][2][4], px[2][4];
   auto load = [&](int t) {
     const int row0 = t * RT;
 #pragma unroll
@@ -206,7 +167,7 @@ __global__ __launch_bounds__(512) void gru_dw_b3(const float* __restrict__ dgi, 
       for (int i = 0; i < 4; ++i) {
         const int row = row0 + 16 * mt + 4 * q + i;
 #pragma unroll
-        for (int j = 0; j < 3; ++j) pd[mt][i][j] = row < M ? D[(size_t)row * G + c0 + 16 * j] : 0.0f;
+        for (int j = 0; j < 3; ++j) pd[j][mt][i] = row < M ? D[(size_t)row * G + c0 + 16 * j] : 0.0f;
       }
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
@@ -232,15 +193,15 @@ __global__ __launch_bounds__(512) void gru_dw_b3(const float* __restrict__ dgi, 
     for (int e = 0; e < 4; ++e) {
       unsigned b[3];
       ctls::split3_pair(px[0][e], px[1][e], b[0], b[1], b[2]);
-#pragma unroll
-      for (int p = 0; p < 3; ++p) *reinterpret_cast<unsigned*>(img + p * PLN + (4 * cq + e) * KR + ks) = b[p];
+      b3::store_pair(img, PLN, KR, 4 * cq + e, rp, b);
     }
-    // the gate gradients of the tile: A[j] = the pieces of k slots 8 q + e = rows 16 (e / 4) + 4 q + e % 4 of gate column c0 + 16 j
+    // the gate gradients of the tile: A[j] = the pieces of this lane's k slots of gate column c0 + 16 j
     uint4 A[3][3];
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
-      const float v[8] = {pd[0][0][j], pd[0][1][j], pd[0][2][j], pd[0][3][j], pd[1][0][j], pd[1][1][j], pd[1][2][j], pd[1][3][j]};
-      split8(v, A[j][0], A[j][1], A[j][2]);
+      float v[8];
+      b3::to_kslots(v, pd[j]);
+      b3::split8(v, A[j]);
       // the tile's eight rows of this lane as a tree, then the running sum
       dbias[j] += ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]));
     }
@@ -250,12 +211,11 @@ __global__ __launch_bounds__(512) void gru_dw_b3(const float* __restrict__ dgi, 
 #pragma unroll
     for (int c = 0; c < 8; ++c) {
       uint4 Bp[3];
+      b3::read3(Bp, bcol + 16 * c * KR, PLN);
+      b3::one_chain([&](int ti, int tj) {
 #pragma unroll
-      for (int p = 0; p < 3; ++p) Bp[p] = *reinterpret_cast<const uint4*>(bcol + p * PLN + 16 * c * KR);
-#pragma unroll
-      for (int k = 0; k < 6; ++k)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) acc[j][c] = mf(A[j][TI[k]], Bp[TJ[k]], acc[j][c]);
+        for (int j = 0; j < 3; ++j) acc[j][c] = b3::mf(A[j][ti], Bp[tj], acc[j][c]);
+      });
     }
   }
   float* base = ws + (size_t)(hh * nwg + wg) * grul::DW_NEL;
@@ -276,11 +236,6 @@ __global__ __launch_bounds__(512) void gru_dw_b3(const float* __restrict__ dgi, 
 
 // ------------------------------------------------------------------------------------------------ C ABI (include/aircombat.h)
 extern "C" {
-static int gru_dense_products_ok(const char* who, int32_t dense_products) {
-  if (dense_products != AC_PRODUCTS_FP32 && dense_products != AC_PRODUCTS_BF16X3)
-    return fail(std::string(who) + ": unknown dense products " + std::to_string(dense_products) + " (AC_PRODUCTS_FP32 or AC_PRODUCTS_BF16X3)");
-  return 0;
-}
 static grul::Dense gru_dense_kernels(int32_t dense_products) {
   if (dense_products == AC_PRODUCTS_FP32) return grul::dense_fp32();
   return {grls::gru_gi_fwd_b3, grls::gru_dw_b3, grls::gru_dx_b3};
@@ -289,7 +244,8 @@ int ac_gru_layer_forward_pd(int32_t device_id, void* stream, int32_t N, int32_t 
                             const float* d_w_ih, const float* d_w_hh, const float* d_b_ih, const float* d_b_hh, const float* d_gamma,
                             const float* d_beta, float eps, float* d_workspace, float* d_out, float* d_h_T, float* d_y, float* d_saved,
                             float* d_stats, int32_t products, int32_t dense_products) {
-  if (gru_products_ok("ac_gru_layer_forward_pd", products) || gru_dense_products_ok("ac_gru_layer_forward_pd", dense_products)) return -1;
+  const char* who = "ac_gru_layer_forward_pd";
+  if (trn::products_ok(who, "products", products) || trn::products_ok(who, "dense products", dense_products)) return -1;
   return gru_layer_forward("ac_gru_layer_forward_pd", products, gru_dense_kernels(dense_products), device_id, stream, N, T, d_x, d_hxs, d_masks,
                            d_w_ih, d_w_hh, d_b_ih, d_b_hh, d_gamma, d_beta, eps, d_workspace, d_out, d_h_T, d_y, d_saved, d_stats);
 }
@@ -298,7 +254,8 @@ int ac_gru_layer_backward_pd(int32_t device_id, void* stream, int32_t N, int32_t
                              const float* d_gamma, const float* d_y, const float* d_saved, const float* d_stats, float* d_workspace,
                              float* d_dx, float* d_dhxs, float* d_dw_ih, float* d_dw_hh, float* d_db_ih, float* d_db_hh, float* d_dgamma,
                              float* d_dbeta, int32_t products, int32_t dense_products) {
-  if (gru_products_ok("ac_gru_layer_backward_pd", products) || gru_dense_products_ok("ac_gru_layer_backward_pd", dense_products)) return -1;
+  const char* who = "ac_gru_layer_backward_pd";
+  if (trn::products_ok(who, "products", products) || trn::products_ok(who, "dense products", dense_products)) return -1;
   return gru_layer_backward("ac_gru_layer_backward_pd", products, gru_dense_kernels(dense_products), device_id, stream, N, T, d_g_out, d_g_h_T,
                             d_x, d_hxs, d_masks, d_w_ih, d_w_hh, d_gamma, d_y, d_saved, d_stats, d_workspace, d_dx, d_dhxs, d_dw_ih, d_dw_hh,
                             d_db_ih, d_db_hh, d_dgamma, d_dbeta);

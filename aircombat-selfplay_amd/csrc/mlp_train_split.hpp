@@ -5,52 +5,46 @@
 // 16 mt + 4 q + i), and for the backward the same partial sets in the same layout, so mlp_block_reduce, the workspace and
 // ac_mlp_block_workspace_floats are shared.
 //
-// The product is gru_train_split.hpp's: every fp32 value is three bf16 pieces (ctls::split3_pair, exact), a product keeps the six terms
-// b_i b_j with i + j <= 2 on v_mfma_f32_16x16x32_bf16, smallest first within a k-step, into fp32 accumulators. K is zero-padded on
-// chip to KP = 32, 64 or 128 (a k-step is 32; KPS below says which of them AC_PRODUCTS_BF16X3 dispatches). W is read from the caller's fp32 tensor at every call and split in
-// registers once per workgroup (12 VGPRs per k-step); nothing is kept between calls. The bias, the ReLU, the LayerNorm statistics and
-// their backward row sums, db, dgamma and dbeta are mlp_train.hpp's fp32 code on unsplit values.
+// The product is bf16x3.hpp's. K is zero-padded on chip to KP = 128 (a k-step is 32; KPS below). W is split once per workgroup. The
+// bias, the ReLU, the LayerNorm statistics and their backward row sums, db, dgamma and dbeta are mlp_train.hpp's fp32 code on unsplit
+// values.
 //
-//   x    split once per tile by the thread that stores it: a thread owns rows 2 rp, 2 rp + 1 and CW adjacent columns. The row-major
-//        image [32][KP + 8] per plane (row strides 80, 144, 272 B: 20, 36, 68 dwords, so 16 consecutive rows' 16-byte reads start
-//        in 16 different groups of four banks, as the planes of the GRU split kernels) is the A operand of z = x Wᵀ. tile_z is the ONE function that forms z, in the forward and in
-//        the backward's recomputation: the same pieces, terms, order and accumulator chain, so the backward's ReLU mask is the
-//        forward's bit for bit.
-//   dW   the sum runs over the tile's rows: k slot 8 q + e of the instruction is row 16 (e / 4) + 4 q + e % 4 (gru_dw_b3), so dz in
-//        the product's result layout IS the A operand, split in registers; x is the B operand from a transposed image [column][k slot]
-//        (80 B per column), which the storing thread writes from the same pieces (a row pair of one column is one 32-bit word).
-//        One accumulator per result for all six terms, over every row the workgroup walks.
+//   x    split once per tile by the thread that stores it: a thread owns rows 2 rp, 2 rp + 1 and four adjacent columns. The row-major
+//        image [32][KP + 8] per plane (272 B rows) is the A operand of z = x Wᵀ. tile_z is the ONE function that forms z, in the
+//        forward and in the backward's recomputation: the same pieces, terms, order and accumulator chain, so the backward's ReLU
+//        mask is the forward's bit for bit.
+//   dW   the sum runs over the tile's rows (k slots), so dz in the product's result layout IS the A operand, split in registers; x
+//        is the B operand from the transposed image, which the storing thread writes from the same pieces. One accumulator per
+//        result for all six terms, over every row the workgroup walks.
 //   dx   dz goes through LDS once as three planes [32][128 + 8] (written in the result layout, read as 16-byte rows) against the
-//        pieces of a transposed register slice of W. Three accumulation chains per result, one per order of the terms, added
-//        smallest first at the end, one 16-row half of the tile after the other: with all 24 terms in one chain dx came out with a
-//        one-sided mean error (-0.044 of its rms error at 4096 x 60, fp32 kernels +0.0002), which the sums over rows downstream
-//        (dbeta and db of the block before) collect: dbeta0 read 1.27 of its bound there.
+//        pieces of a transposed register slice of W. Three chains per result, one per order of the terms (chains_by_order, and
+//        why), one 16-row half of the tile after the other.
+// The weight slices here are guarded (k < K, and 0 beyond K in a column), so they stay in this file: folding them into
+// b3::row_slice / col_slice would put a run-time test into the GRU kernels. An aligned, unpadded row takes b3::read8.
 // No floating-point atomics: results are bit-identical from run to run.
 #pragma once
 
 namespace mlps {
 using mlpt::floatx4; using mlpt::H; using mlpt::RT; using mlpt::HP; using mlpt::wave_sum; using mlpt::sum16;
-using grus::mf; using grus::split8;
 constexpr int KR = RT + 8;   // k slots per column of the transposed x image
 constexpr int KZ = H + 8;    // bf16 per plane row of the dz tile
-constexpr int TI[6] = {2, 1, 0, 1, 0, 0}, TJ[6] = {0, 1, 2, 0, 1, 0};   // the six terms (A piece, B piece), smallest first
 // The KP values AC_PRODUCTS_BF16X3 runs split (ac_mlp_block_constant(3)). A forward and its backward must form z the same way, so a KP
 // is in only when its forward and both its backwards met the condition of profiles/mlp_split_bench.txt (measured with 32 | 64 | 128
 // here): KP = 128 did, 0.67 - 0.71 / 0.79 / 0.84 of the fp32 kernels' time; KP = 64 without dx tied (0.170 ms both) and KP = 32 was slower
-// than the fp32 form (which pads K <= 16 to 16 only). Their instantiations stay below as the forms that were measured.
+// than the fp32 form (which pads K <= 16 to 16 only). Those two were removed; the kernels below are instantiated for KP = 128 alone.
 constexpr int KPS = 128;
 
-// this thread's share of an x tile: rows 2 rp and 2 rp + 1, columns CW cq .. CW cq + CW - 1 (at KP = 32 half the threads own one)
+// this thread's share of an x tile: rows 2 rp and 2 rp + 1, columns CW cq .. CW cq + CW - 1
 template <int KP>
 struct Patch {
-  static constexpr int CW = KP >= 64 ? KP / 32 : 2;
+  static constexpr int CW = KP / 32;
+  static_assert(CW == 4, "512 threads own 16 row pairs x 32 column groups of four: KP = 128");
   static constexpr int KS = KP + 8, PLN = RT * KS, PLNT = KP * KR;
   float v[2][CW];
 
-  // rows >= M and columns >= K are 0. vec: K == KP and src 16-byte aligned (then rows are at least 8-byte aligned at every column pair)
+  // rows >= M and columns >= K are 0. vec: K == KP and src 16-byte aligned
   __device__ __forceinline__ void load(const float* __restrict__ src, int K, int M, int row0, int tid, int vec) {
     const int rp = tid & 15, cq = tid >> 4, c = CW * cq;
-    if (c >= KP) return;
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
       const int row = row0 + 2 * rp + k;
@@ -58,17 +52,8 @@ struct Patch {
       for (int e = 0; e < CW; ++e) v[k][e] = 0.0f;
       if (row < M) {
         if (vec) {
-          const float* p = src + (size_t)row * KP + c;
-          if constexpr (CW == 2) {
-            const float2 t = *reinterpret_cast<const float2*>(p);
-            v[k][0] = t.x; v[k][1] = t.y;
-          } else {
-#pragma unroll
-            for (int e = 0; e < CW; e += 4) {
-              const float4 t = *reinterpret_cast<const float4*>(p + e);
-              v[k][e] = t.x; v[k][e + 1] = t.y; v[k][e + 2] = t.z; v[k][e + 3] = t.w;
-            }
-          }
+          const float4 t = *reinterpret_cast<const float4*>(src + (size_t)row * KP + c);
+          v[k][0] = t.x; v[k][1] = t.y; v[k][2] = t.z; v[k][3] = t.w;
         } else {
 #pragma unroll
           for (int e = 0; e < CW; ++e)
@@ -82,31 +67,22 @@ struct Patch {
   template <bool TR>
   __device__ __forceinline__ void store(unsigned short* xr, unsigned short* xt, int tid) const {
     const int rp = tid & 15, cq = tid >> 4, c = CW * cq;
-    if (c >= KP) return;
     unsigned w[2][CW / 2][3];
 #pragma unroll
-    for (int k = 0; k < 2; ++k)
+    for (int k = 0; k < 2; ++k) b3::split_row(w[k], v[k]);
 #pragma unroll
-      for (int e = 0; e < CW / 2; ++e) ctls::split3_pair(v[k][2 * e], v[k][2 * e + 1], w[k][e][0], w[k][e][1], w[k][e][2]);
-#pragma unroll
-    for (int k = 0; k < 2; ++k)
-#pragma unroll
-      for (int p = 0; p < 3; ++p) {
-        unsigned short* at = xr + p * PLN + (2 * rp + k) * KS + c;
-        if constexpr (CW == 2) *reinterpret_cast<unsigned*>(at) = w[k][0][p];
-        else if constexpr (CW == 4) *reinterpret_cast<uint2*>(at) = make_uint2(w[k][0][p], w[k][1][p]);
-        else *reinterpret_cast<uint4*>(at) = make_uint4(w[k][0][p], w[k][1][p], w[k][2][p], w[k][3][p]);
-      }
+    for (int k = 0; k < 2; ++k) b3::store_words(xr + (2 * rp + k) * KS + c, PLN, w[k]);
     if constexpr (TR) {
-      const int ks = 8 * ((rp >> 1) & 3) + 4 * (rp >> 3) + 2 * (rp & 1);   // the k slot of row 2 rp; row 2 rp + 1 has the next
 #pragma unroll
-      for (int e = 0; e < CW; ++e)
+      for (int e = 0; e < CW; ++e) {
+        unsigned pair[3];   // column c + e of both rows, from the words that hold columns (c + e) & ~1 and the next
 #pragma unroll
         for (int p = 0; p < 3; ++p) {
           const unsigned w0 = w[0][e / 2][p], w1 = w[1][e / 2][p];
-          const unsigned pair = (e & 1) ? ((w0 >> 16) | (w1 & 0xffff0000u)) : ((w0 & 0xffffu) | (w1 << 16));
-          *reinterpret_cast<unsigned*>(xt + p * PLNT + (c + e) * KR + ks) = pair;
+          pair[p] = (e & 1) ? ((w0 >> 16) | (w1 & 0xffff0000u)) : ((w0 & 0xffffu) | (w1 << 16));
         }
+        b3::store_pair(xt, PLNT, KR, c + e, rp, pair);
+      }
     }
   }
 };
@@ -119,14 +95,12 @@ __device__ __forceinline__ void load_w(uint4 (&B)[KP / 32][3], const float* __re
     const int k0 = 32 * s + 8 * q;
     float v[8];
     if (vec) {
-      const float* p = w + (size_t)u * KP + k0;
-      const float4 v0 = *reinterpret_cast<const float4*>(p), v1 = *reinterpret_cast<const float4*>(p + 4);
-      v[0] = v0.x; v[1] = v0.y; v[2] = v0.z; v[3] = v0.w; v[4] = v1.x; v[5] = v1.y; v[6] = v1.z; v[7] = v1.w;
+      b3::read8(v, w + (size_t)u * KP + k0);
     } else {
 #pragma unroll
       for (int e = 0; e < 8; ++e) v[e] = k0 + e < K ? w[(size_t)u * K + k0 + e] : 0.0f;
     }
-    split8(v, B[s][0], B[s][1], B[s][2]);
+    b3::split8(v, B[s]);
   }
 }
 
@@ -142,14 +116,11 @@ __device__ __forceinline__ void tile_z(floatx4 (&acc)[2], const unsigned short* 
   for (int s = 0; s < KP / 32; ++s) {
     uint4 A[2][3];
 #pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-      for (int p = 0; p < 3; ++p) A[mt][p] = *reinterpret_cast<const uint4*>(arow + p * PLN + 16 * mt * KS + 32 * s);
-#pragma unroll
-    for (int k = 0; k < 6; ++k) {
-      acc[0] = mf(A[0][TI[k]], B[s][TJ[k]], acc[0]);
-      acc[1] = mf(A[1][TI[k]], B[s][TJ[k]], acc[1]);
-    }
+    for (int mt = 0; mt < 2; ++mt) b3::read3(A[mt], arow + 16 * mt * KS + 32 * s, PLN);
+    b3::one_chain([&](int i, int j) {
+      acc[0] = b3::mf(A[0][i], B[s][j], acc[0]);
+      acc[1] = b3::mf(A[1][i], B[s][j], acc[1]);
+    });
   }
 }
 
@@ -218,16 +189,15 @@ __global__ __launch_bounds__(512) void mlp_block_bwd_b3(const float* __restrict_
   const int u = 16 * wv + n;
   uint4 B[KP / 32][3];   // the recomputed z
   load_w<KP>(B, w, K, u, q, vecw);
-  const bool do_dx = DX && 16 * wv < KP;
-  const int kc = 16 * wv + n;   // this lane's column of dx
+  const int kc = 16 * wv + n;   // this lane's column of dx (the eight waves cover KP = 128)
   uint4 Bx[DX ? 4 : 1][3];      // the pieces of W[unit 32 s + 8 q + e][column kc]: dx = dz W sums over units
   if constexpr (DX) {
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
       float v[8];
 #pragma unroll
-      for (int e = 0; e < 8; ++e) v[e] = (do_dx && kc < K) ? w[(size_t)(32 * s + 8 * q + e) * K + kc] : 0.0f;
-      split8(v, Bx[s][0], Bx[s][1], Bx[s][2]);
+      for (int e = 0; e < 8; ++e) v[e] = kc < K ? w[(size_t)(32 * s + 8 * q + e) * K + kc] : 0.0f;
+      b3::split8(v, Bx[s]);
     }
   }
   const float bias = b[u], gam = gamma[u];
@@ -309,54 +279,44 @@ __global__ __launch_bounds__(512) void mlp_block_bwd_b3(const float* __restrict_
         dz[mt][i] = pos[mt][i] ? da : 0.0f;
         dbias += dz[mt][i];
       }
-      if constexpr (DX) grus::write_column(&dzs[0][0][0] + (16 * mt + 4 * q) * KZ + u, PLNZ, KZ, dz[mt]);
+      if constexpr (DX) b3::write_column(&dzs[0][0][0] + (16 * mt + 4 * q) * KZ + u, PLNZ, KZ, dz[mt]);
     }
-    // dW += dz^T x: the tile's 32 rows are one k-step; A = the pieces of dz (k slot 8 q + e = row 16 (e / 4) + 4 q + e % 4 of unit
-    // 16 w + n), B = the pieces of x[that row][column 16 c + n] from the transposed image
+    // dW += dz^T x: the tile's 32 rows are one k-step; A = the pieces of dz of unit 16 w + n (this lane's k slots), B = the pieces
+    // of x[those rows][column 16 c + n] from the transposed image
     {
-      const float v[8] = {dz[0][0], dz[0][1], dz[0][2], dz[0][3], dz[1][0], dz[1][1], dz[1][2], dz[1][3]};
+      float v[8];
+      b3::to_kslots(v, dz);
       uint4 A[3];
-      split8(v, A[0], A[1], A[2]);
+      b3::split8(v, A);
       const unsigned short* bcol = &xt[0][0][0] + n * KR + 8 * q;
 #pragma unroll
       for (int c = 0; c < NJ; c += 2) {
         uint4 Bp[2][3];
 #pragma unroll
-        for (int h = 0; h < 2; ++h)
-#pragma unroll
-          for (int p = 0; p < 3; ++p) Bp[h][p] = *reinterpret_cast<const uint4*>(bcol + p * PLNT + 16 * (c + h) * KR);
-#pragma unroll
-        for (int k = 0; k < 6; ++k) {
-          accw[c] = mf(A[TI[k]], Bp[0][TJ[k]], accw[c]);
-          accw[c + 1] = mf(A[TI[k]], Bp[1][TJ[k]], accw[c + 1]);
-        }
+        for (int h = 0; h < 2; ++h) b3::read3(Bp[h], bcol + 16 * (c + h) * KR, PLNT);
+        b3::one_chain([&](int i, int j) {
+          accw[c] = b3::mf(A[i], Bp[0][j], accw[c]);
+          accw[c + 1] = b3::mf(A[i], Bp[1][j], accw[c + 1]);
+        });
       }
     }
     __syncthreads();   // dzs complete; and every read of xr, xt, st, part of this tile is behind
-    if (do_dx) {   // (false at compile time without DX)
-      // one accumulation chain per order of the terms (i + j = 2, 1, 0), added smallest first at the end: dx is summed over rows
-      // downstream (dbeta and db of the block before), and the matrix instruction's accumulation leans to one side by a small
-      // fraction of the accumulator's last place per step, so only the four b0 b0 steps run at the result's own magnitude
+    if constexpr (DX) {
+      // dx is summed over rows downstream (dbeta and db of the block before): one chain per order of the terms
 #pragma unroll
       for (int mt = 0; mt < 2; ++mt) {
-        floatx4 c0 = {0.0f, 0.0f, 0.0f, 0.0f}, c1 = c0, c2 = c0;
+        floatx4 c[3] = {};
         const unsigned short* arow = &dzs[0][0][0] + (16 * mt + n) * KZ + 8 * q;
 #pragma unroll
-        for (int s = 0; s < (DX ? 4 : 0); ++s) {
+        for (int s = 0; s < 4; ++s) {
           uint4 A[3];
-#pragma unroll
-          for (int p = 0; p < 3; ++p) A[p] = *reinterpret_cast<const uint4*>(arow + p * PLNZ + 32 * s);
-          c0 = mf(A[2], Bx[s][0], c0);
-          c1 = mf(A[1], Bx[s][0], c1);
-          c2 = mf(A[0], Bx[s][0], c2);
-          c0 = mf(A[1], Bx[s][1], c0);
-          c1 = mf(A[0], Bx[s][1], c1);
-          c0 = mf(A[0], Bx[s][2], c0);
+          b3::read3(A, arow + 32 * s, PLNZ);
+          b3::chains_by_order(c, A, Bx[s]);
         }
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           const int row = row0 + 16 * mt + 4 * q + i;
-          if (row < M && kc < K) dx[(size_t)row * K + kc] = (c0[i] + c1[i]) + c2[i];
+          if (row < M && kc < K) dx[(size_t)row * K + kc] = b3::chain_sum(c, i);
         }
       }
     }
@@ -383,16 +343,13 @@ __global__ __launch_bounds__(512) void mlp_block_bwd_b3(const float* __restrict_
 
 // ------------------------------------------------------------------------------------------------ C ABI (include/aircombat.h)
 extern "C" {
-static int mlp_products_ok(const char* who, int32_t products) {
-  if (products != AC_PRODUCTS_FP32 && products != AC_PRODUCTS_BF16X3)
-    return fail(std::string(who) + ": unknown products " + std::to_string(products) + " (AC_PRODUCTS_FP32 or AC_PRODUCTS_BF16X3)");
-  return 0;
-}
-// the KP of the split form (a k-step is 32), or 0 where `products` runs the fp32 kernels
+// the KP of the split form (a k-step is 32), or 0 where `products` runs the fp32 kernels: the one place that decides. A KP named in
+// mlps::KPS needs its instantiations in the two entries below.
 static int mlp_split_kp(int32_t K, int32_t products) {
   const int kp = K <= 32 ? 32 : mlp_kp(K);
   return (products == AC_PRODUCTS_BF16X3 && (mlps::KPS & kp)) ? kp : 0;
 }
+static_assert(mlps::KPS == 128, "the entries below launch the KP = 128 kernels for every K that mlp_split_kp lets through");
 static int mlp_split_vec(const void* p, int32_t K, int kp) { return K == kp && trn::aligned16(p); }
 
 int32_t ac_mlp_block_constant(int32_t which) {
@@ -407,7 +364,7 @@ int32_t ac_mlp_block_constant(int32_t which) {
 
 int ac_mlp_block_forward_p(int32_t device_id, void* stream, int32_t M, int32_t K, float eps, const float* d_x, const float* d_w, const float* d_b,
                            const float* d_gamma, const float* d_beta, float* d_y, float* d_stats, int32_t products) {
-  if (mlp_products_ok("ac_mlp_block_forward_p", products)) return -1;
+  if (trn::products_ok("ac_mlp_block_forward_p", "products", products)) return -1;
   if (!d_x || !d_w || !d_b || !d_gamma || !d_beta || !d_y) return fail("ac_mlp_block_forward_p: null argument");
   if (mlp_shape_ok("ac_mlp_block_forward_p", M, K)) return -1;
   const int kp = mlp_split_kp(K, products);
@@ -415,15 +372,8 @@ int ac_mlp_block_forward_p(int32_t device_id, void* stream, int32_t M, int32_t K
   HIP_OK(hipSetDevice(device_id));
   const dim3 grid(trn::capped_tiles(M, mlpt::RT, mlpt::FWD_WGS)), block(512);
   const int vecx = mlp_split_vec(d_x, K, kp), vecw = mlp_split_vec(d_w, K, kp);
-#define AC_MLP_FWD(KP)                                                                                                                         \
-  hipLaunchKernelGGL(mlps::mlp_block_fwd_b3<KP>, grid, block, 0, (hipStream_t)stream, d_x, d_w, d_b, d_gamma, d_beta, d_y, d_stats, (int)M, \
-                     (int)K, eps, vecx, vecw)
-  switch (kp) {
-    case 32: AC_MLP_FWD(32); break;
-    case 64: AC_MLP_FWD(64); break;
-    default: AC_MLP_FWD(128); break;
-  }
-#undef AC_MLP_FWD
+  hipLaunchKernelGGL(mlps::mlp_block_fwd_b3<mlps::KPS>, grid, block, 0, (hipStream_t)stream, d_x, d_w, d_b, d_gamma, d_beta, d_y, d_stats,
+                     (int)M, (int)K, eps, vecx, vecw);
   HIP_OK(hipGetLastError());
   return 0;
 }
@@ -431,7 +381,7 @@ int ac_mlp_block_forward_p(int32_t device_id, void* stream, int32_t M, int32_t K
 int ac_mlp_block_backward_p(int32_t device_id, void* stream, int32_t M, int32_t K, const float* d_dy, const float* d_x, const float* d_w,
                             const float* d_b, const float* d_gamma, const float* d_stats, float* d_workspace, float* d_dx, float* d_dw,
                             float* d_db, float* d_dgamma, float* d_dbeta, int32_t products) {
-  if (mlp_products_ok("ac_mlp_block_backward_p", products)) return -1;
+  if (trn::products_ok("ac_mlp_block_backward_p", "products", products)) return -1;
   if (!d_dy || !d_x || !d_w || !d_b || !d_gamma || !d_stats || !d_workspace || !d_dw || !d_db || !d_dgamma || !d_dbeta)
     return fail("ac_mlp_block_backward_p: null argument");
   if (mlp_shape_ok("ac_mlp_block_backward_p", M, K)) return -1;
@@ -442,19 +392,8 @@ int ac_mlp_block_backward_p(int32_t device_id, void* stream, int32_t M, int32_t 
   const int G = trn::capped_tiles(M, mlpt::RT, mlpt::BWD_WGS);
   const dim3 grid(G), block(512);
   const int vecx = mlp_split_vec(d_x, K, kp), vecw = mlp_split_vec(d_w, K, kp);
-#define AC_MLP_BWD(KP)                                                                                                                             \
-  if (d_dx)                                                                                                                                        \
-    hipLaunchKernelGGL((mlps::mlp_block_bwd_b3<KP, true>), grid, block, 0, (hipStream_t)stream, d_dy, d_x, d_w, d_b, d_gamma, d_stats, d_workspace, \
-                       d_dx, (int)M, (int)K, vecx, vecw);                                                                                          \
-  else                                                                                                                                             \
-    hipLaunchKernelGGL((mlps::mlp_block_bwd_b3<KP, false>), grid, block, 0, (hipStream_t)stream, d_dy, d_x, d_w, d_b, d_gamma, d_stats, d_workspace, \
-                       d_dx, (int)M, (int)K, vecx, vecw)
-  switch (kp) {
-    case 32: AC_MLP_BWD(32); break;
-    case 64: AC_MLP_BWD(64); break;
-    default: AC_MLP_BWD(128); break;
-  }
-#undef AC_MLP_BWD
+  hipLaunchKernelGGL((d_dx ? mlps::mlp_block_bwd_b3<mlps::KPS, true> : mlps::mlp_block_bwd_b3<mlps::KPS, false>), grid, block, 0,
+                     (hipStream_t)stream, d_dy, d_x, d_w, d_b, d_gamma, d_stats, d_workspace, d_dx, (int)M, (int)K, vecx, vecw);
   HIP_OK(hipGetLastError());
   const int nel = mlpt::H * K + 3 * mlpt::H;
   hipLaunchKernelGGL(mlpt::mlp_block_reduce, dim3((nel + 255) / 256), dim3(256), 0, (hipStream_t)stream, (const float*)d_workspace, G, (int)K, d_dw,

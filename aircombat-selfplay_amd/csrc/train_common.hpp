@@ -29,6 +29,13 @@ inline int rows_fit_i32(const std::string& who, int32_t M, int width, int slack)
   return 0;
 }
 
+// -1 with the message unless `code` is one of the AC_PRODUCTS_ values; `word` names the argument: "products" or "dense products"
+inline int products_ok(const char* who, const char* word, int32_t code) {
+  if (code != AC_PRODUCTS_FP32 && code != AC_PRODUCTS_BF16X3)
+    return fail(std::string(who) + ": unknown " + word + " " + std::to_string(code) + " (AC_PRODUCTS_FP32 or AC_PRODUCTS_BF16X3)");
+  return 0;
+}
+
 __host__ __device__ __forceinline__ bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 inline bool aligned16(std::initializer_list<const void*> ps) {
   for (const void* p : ps)

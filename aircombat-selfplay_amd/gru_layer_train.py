@@ -21,7 +21,7 @@ import torch
 from . import gru_train
 from .gru_train import HID, SAVED, DeviceGRULayer
 from .policy import UnsupportedPolicy
-from .train_common import Launch, layernorm_faults, swap_children
+from .train_common import Launch, layernorm_faults, products_code, swap_children
 
 
 class DeviceGRULayerFunction(torch.autograd.Function):
@@ -72,17 +72,15 @@ class DeviceGRULayerFunction(torch.autograd.Function):
 
 
 def dense_products_code(dense_products):
-    """The library's constant for ``dense_products``; ValueError for anything but "fp32" / "bf16x3"."""
-    if not isinstance(dense_products, str) or dense_products not in gru_train.PRODUCTS:
-        raise ValueError(f"dense_products must be one of {', '.join(map(repr, gru_train.PRODUCTS))}, not {dense_products!r}")
-    return gru_train.PRODUCTS[dense_products]
+    """train_common.products_code for the argument ``dense_products``."""
+    return products_code(dense_products, "dense_products")
 
 
 def gru_layer(x, hxs, masks, w_ih, w_hh, b_ih, b_hh, gamma, beta, eps=1e-5, products="fp32", dense_products="fp32"):
     """The whole layer as a function: DeviceGRULayerFunction with its ``save`` decided here (grad mode on and some input requiring
     grad). x [T*N, 128], hxs [N, 128], masks [T*N], float32 on one CUDA device -> (out [T*N, 128], h_T [N, 128]). ``products`` selects
     the recurrence kernels' product, ``dense_products`` that of gi, dx and the weight gradients."""
-    code, dense = gru_train.products_code(products), dense_products_code(dense_products)
+    code, dense = products_code(products), dense_products_code(dense_products)
     for name, t in (("x", x), ("hxs", hxs), ("masks", masks)):   # no torch op inside would notice: the kernels read float32 as given
         if t.dtype != torch.float32 or t.device != w_ih.device:
             raise UnsupportedPolicy(f"gru_layer: {name} is {t.dtype} on {t.device} (only float32 on {w_ih.device})")
@@ -145,7 +143,7 @@ def use_device_gru_layer(module, products=None, dense_products=None):
     is touched. ``dense_products`` likewise: None keeps a DeviceFusedGRULayer's own (one that is handed in as the module's child stays as
     it is: only other layers are swapped) and means "fp32" for anything else. Returns the number of layers swapped."""
     if products is not None:
-        gru_train.products_code(products)
+        products_code(products)
     if dense_products is not None:
         dense_products_code(dense_products)
 

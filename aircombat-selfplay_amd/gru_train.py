@@ -16,18 +16,10 @@ import torch
 import torch.nn as nn
 
 from .policy import UnsupportedPolicy
-from .train_common import Launch, swap_children
+from .train_common import PRODUCTS, Launch, products_code, swap_children   # noqa: F401  (PRODUCTS, products_code: also this module's names)
 
 HID = 128
 SAVED = 4 * HID   # floats per (step, row) the forward keeps for the backward: r, z, n, W_hn h + b_hn
-PRODUCTS = {"fp32": 0, "bf16x3": 1}   # AC_PRODUCTS_FP32, AC_PRODUCTS_BF16X3 (include/aircombat.h)
-
-
-def products_code(products):
-    """The library's constant for ``products``; ValueError for anything but "fp32" / "bf16x3"."""
-    if not isinstance(products, str) or products not in PRODUCTS:
-        raise ValueError(f"products must be one of {', '.join(map(repr, PRODUCTS))}, not {products!r}")
-    return PRODUCTS[products]
 
 
 class DeviceGRUFunction(torch.autograd.Function):

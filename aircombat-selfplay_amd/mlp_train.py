@@ -15,9 +15,8 @@ per value on the bf16 matrix instruction (csrc/mlp_train_split.hpp); the default
 import torch
 import torch.nn as nn
 
-from .gru_train import products_code
 from .policy import UnsupportedPolicy
-from .train_common import Launch, layernorm_faults, linear_faults, swap_children
+from .train_common import Launch, layernorm_faults, linear_faults, products_code, swap_children
 
 HID = 128      # out-features of every block, the LayerNorm's width
 K_MAX = 256    # in-features at most

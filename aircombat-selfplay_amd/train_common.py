@@ -10,6 +10,15 @@ from . import capi
 from .policy import UnsupportedPolicy
 
 HID = 128   # the width of every LayerNorm the kernels run
+PRODUCTS = {"fp32": 0, "bf16x3": 1}   # AC_PRODUCTS_FP32, AC_PRODUCTS_BF16X3 (include/aircombat.h)
+
+
+def products_code(value, name="products"):
+    """The library's constant for ``value``, the argument called ``name`` ("products" or "dense_products"); ValueError for anything but
+    "fp32" / "bf16x3"."""
+    if not isinstance(value, str) or value not in PRODUCTS:
+        raise ValueError(f"{name} must be one of {', '.join(map(repr, PRODUCTS))}, not {value!r}")
+    return PRODUCTS[value]
 
 
 class Launch:

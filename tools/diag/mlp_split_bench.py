@@ -6,9 +6,12 @@ For each (N chunks, T) shape, M = N T rows, three consecutive runs, each the med
 (products="fp32", "bf16x3") alternating call by call on the same tensors (device = HIP events around each call, wall = per call with a
 synchronise):
 
-a. the kernels one by one, per K in 15, 32, 64, 128 (KP = 32, 32, 64, 128; the fp32 form pads K = 15 to 16): the forward call in its inference form (no statistics kept), the
-   backward call with dx and the backward call without dx (each backward call is the block's kernel plus the same small sum of the
-   partials in both forms);
+a. the kernels one by one, per K in 15, 32, 64, 128 (the fp32 form pads K = 15 to 16): the forward call in its inference form (no
+   statistics kept), the backward call with dx and the backward call without dx (each backward call is the block's kernel plus the
+   same small sum of the partials in both forms). Only KP = 128 has split kernels (mlps::KPS), so at K <= 64 both legs run the fp32
+   kernels and tie. Part 1 of profiles/mlp_split_bench.txt, measured with KP = 32, 64 and 128 dispatched, cannot be reproduced from
+   this tree: the KP = 32 and 64 instantiations were removed after it, and measuring another dispatch mask needs the commit that
+   added the split blocks, built with KPS = 32 | 64 | 128;
 b. the forward + backward calls with dx at K = 128 and without dx at K = 15 (a head's block and an observation's);
 c. a two-block DeviceMLPLayer, forward + backward: 128 -> 128 -> 128 with a gradient for x and 15 -> 128 -> 128 without;
 d. one actor + critic minibatch of the tests' restated policy through DevicePPOTrainer.ppo_update, the fused GRU layer in its bf16x3
@@ -203,7 +206,7 @@ def main():
     ap.add_argument("--shapes", default="")
     ap.add_argument("--parent-lib", default="", help="libaircombat_hip.so built from the parent commit, for leg e")
     ap.add_argument("--no-errors", action="store_true", help="skip the error table at 4096 x 60")
-    ap.add_argument("--append", action="store_true", help="add to --out instead of replacing it (a second run on another dispatch mask)")
+    ap.add_argument("--append", action="store_true", help="add to --out instead of replacing it (a second part of the same file)")
     ap.add_argument("--trace", default="", help="NxT: the C calls in both forms at that shape, for a rocprofv3 kernel trace")
     ap.add_argument("--stats", default=None, help="directory of the kernel traces: <stats>/<N>x<T>/**/*kernel_stats.csv")
     a = ap.parse_args()
