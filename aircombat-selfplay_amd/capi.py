@@ -260,6 +260,8 @@ SIGNATURES = {
     "ac_step_host_wait": (C.c_int, [_p]),
     "ac_step_host": (C.c_int, [_p, C.c_int32]),
     "ac_step_host_actions": (C.c_int, [_p, C.c_int32, _p, C.c_size_t]),
+    "ac_step_host_actions_begin": (C.c_int, [_p, C.c_int32, _p, C.c_size_t]),
+    "ac_step_host_actions_wait": (C.c_int, [_p]),
     "ac_late_config": (C.c_int, [_p, C.c_double, C.c_int32, C.c_int32, C.c_int32]),
     "ac_late_stats": (C.c_int, [_p, _p]),   # (AcLateStats by reference)
     "ac_order_after": (C.c_int, [_p, _p]),

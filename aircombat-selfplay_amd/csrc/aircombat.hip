@@ -2439,15 +2439,19 @@ int ac_step_host(ac_env_t* h, int32_t set) {   // step_async + step_wait in one 
   if (ac_step_host_async(h, set)) return -1;
   return ac_step_host_wait(h);
 }
-// The same from the caller's own array: header word, doorbell, copy, wait (host_step). What the step kernel's retry counter holds after
-// the wait goes into the handle's statistics.
-int ac_step_host_actions(ac_env_t* h, int32_t set, const float* actions, size_t n_floats) {
+// The same from the caller's own array, in two halves: header word, doorbell, copy (host_step) -- and the wait. What the step kernel's
+// retry counter holds after the wait goes into the handle's statistics. Between the halves the caller may do host work of its own
+// (the native VecEnv.step builds its result objects there, csrc/native_step.cpp): the kernel is running.
+int ac_step_host_actions_begin(ac_env_t* h, int32_t set, const float* actions, size_t n_floats) {
   if (!h || !actions || set < 0 || set >= AC_HOST_SETS) return fail("ac_step_host_actions: bad argument");
   if (!h->have_hs[set]) return fail("ac_step_host_actions: call ac_host_buffers for this set first");
   if (n_floats != (size_t)h->N * h->act_dim) return fail("ac_step_host_actions: n_floats is not num_envs * num_agents * act_dim");
   HIP_OK(hipSetDevice(h->device));
   h->late_set = -1;
-  if (host_step(h, set, actions)) return -1;
+  return host_step(h, set, actions);
+}
+int ac_step_host_actions_wait(ac_env_t* h) {
+  if (!h) return fail("ac_step_host_actions_wait: null handle");
   const int ls = h->late_set;
   std::chrono::steady_clock::time_point t0;
   if (ls >= 0 && h->late_timing) t0 = std::chrono::steady_clock::now();
@@ -2477,6 +2481,10 @@ int ac_step_host_actions(ac_env_t* h, int32_t set, const float* actions, size_t 
     h->late_set = -1;
   }
   return rc;
+}
+int ac_step_host_actions(ac_env_t* h, int32_t set, const float* actions, size_t n_floats) {
+  if (ac_step_host_actions_begin(h, set, actions, n_floats)) return -1;
+  return ac_step_host_actions_wait(h);
 }
 int ac_late_config(ac_env_t* h, double fraction, int32_t budget, int32_t delay_us, int32_t timing) {
   if (!h) return fail("ac_late_config: null handle");

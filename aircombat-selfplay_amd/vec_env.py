@@ -29,6 +29,11 @@ from . import capi
 from .config import config_from_yaml, default_config
 from .snapshot import EnvSnapshot, MultiSnapshot, SnapshotMismatch, check_compatible, decode_header
 
+try:    # csrc/native_step.cpp, built by __graft_entry__.build() where Python.h is installed: step() without the interpreter
+    from . import _native_step
+except ImportError:
+    _native_step = None
+
 DONE_MESSAGES = {
     0: "", 1: "altitude is too low", 2: "is on an extreme state", 3: "acceleration is too high", 4: "has been shot down",
     5: "has crashed", 6: "mission completed", 7: "step limits", 8: "unreached heading",
@@ -260,6 +265,21 @@ class HipVecEnv:
         self._results = [self._result(st) for st in self._sets]
         self._step_host = self.lib.ac_step_host_actions
         self._ref0 = self._refs(self._sets[0])   # what a set's arrays count when only this object holds them
+        # step() in one native call: set choice, action pointer, result objects and the wait in C++ (csrc/native_step.cpp), with the
+        # objects built while the kernel runs. AIRCOMBAT_NATIVE_STEP=0 keeps the code below; so does a build without Python.h.
+        self._native = None
+        if _native_step is not None and os.environ.get("AIRCOMBAT_NATIVE_STEP", "1") != "0":
+            dll = self.lib.dll
+            self._native = _native_step.Stepper(C.cast(dll.ac_step_host_actions_begin, C.c_void_p).value,
+                                                C.cast(dll.ac_step_host_actions_wait, C.c_void_p).value, self._h.value,
+                                                self._actions.size, self.copy, len(self._sets[0]["out"]) == 5, LazyInfos, self.lib.check)
+            for st in self._sets:
+                self._native_add(st)
+
+    def _native_add(self, st):
+        """Tell the native step about ring set `st` (its baseline reference counts are taken now: the set's entry of _results exists)."""
+        if self._native is not None:
+            self._native.add_set(st["out"], self._results[st["index"]])
 
     def _add_set(self):
         k = len(self._sets)
@@ -309,6 +329,7 @@ class HipVecEnv:
         if n < RING_SETS:
             st = self._add_set()
             self._results.append(self._result(st))
+            self._native_add(st)
             self._cur = st["index"]
             return st, False
         if self._staging is None:
@@ -383,15 +404,25 @@ class HipVecEnv:
         return o[0].copy(), o[1].copy(), o[2].copy(), LazyInfos(o[3], snapshot=True)
 
     def step(self, actions):
-        """VecEnv.step = step_async + step_wait (env_wrappers.py:30-42), through one library call."""
+        """VecEnv.step = step_async + step_wait (env_wrappers.py:30-42), through one library call -- and where the native step is built,
+        through one native call that does everything below itself (None from it: this step is not one it takes)."""
+        native = self._native
+        if native is not None:
+            res = native.step(self, actions)
+            if res is not None:
+                return res
         assert not self.closed, "Trying to operate on a HipVecEnv after calling close()"
-        st, staged = self._next_set()
         # the library copies the batch into the set itself, where the kernel form allows under the launch (ac_step_host_actions)
         a = actions
         if not (isinstance(a, np.ndarray) and a.dtype == np.float32 and a.flags.c_contiguous):
             a = np.ascontiguousarray(actions, dtype=np.float32)
         if a.size != self._actions.size:
             a = a.reshape(self._actions.shape)    # (raises like the copy into the set's buffer would)
+        if native is not None and a is not actions:
+            res = native.step(self, a)            # converted: now it is the ring alone that decides
+            if res is not None:
+                return res
+        st, staged = self._next_set()
         try:
             addr = C.addressof(C.c_char.from_buffer(a))
         except (TypeError, ValueError):           # a read-only array
@@ -506,6 +537,9 @@ class HipVecEnv:
         cur = getattr(self, "_curriculum", None)
         if cur is not None:                                     # (ac_destroy frees the bank: its views must not outlive it)
             cur.close()
+        if getattr(self, "_native", None) is not None:         # (it holds the sets' tuples and the handle's address)
+            self._native.clear()
+        self._native = None
         if self.copy:
             for st in self._sets:
                 if self._held(st):

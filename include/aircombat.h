@@ -155,6 +155,12 @@ int ac_step_host(ac_env_t* h, int32_t set);   /* both in one call: VecEnv.step (
  * times; then the call returns -1 ("... did not reach the device within the retry budget ...") and every later step does until
  * ac_reset. Every other kernel form, and a handle off the AQL path, copies first, untagged, and then behaves like ac_step_host. */
 int ac_step_host_actions(ac_env_t* h, int32_t set, const float* actions, size_t n_floats);
+/* The two halves of that call: _begin returns once the doorbell is rung and the batch copied (`actions` is not read after it), _wait
+ * blocks until the step is complete and reports like ac_step_host_wait. Host work placed between them runs while the kernel does
+ * (the native VecEnv.step, csrc/native_step.cpp, builds what it returns there). After a _begin that returned 0 call _wait exactly once,
+ * from the same thread, before any other call on the handle; after one that failed, do not. */
+int ac_step_host_actions_begin(ac_env_t* h, int32_t set, const float* actions, size_t n_floats);
+int ac_step_host_actions_wait(ac_env_t* h);
 #define AC_LATE_FRACTION_DEFAULT 1.0    /* share of the batch copied behind the doorbell (profiles/late_actions_summary.txt) */
 #define AC_LATE_BUDGET_DEFAULT 400000   /* tries of ~1.6 us each (a sleep and a read across PCIe): 0.6 s, well under the 10 s AQL deadline */
 #define AC_LATE_WINDOW 1024                  /* late steps per window of the self-check */

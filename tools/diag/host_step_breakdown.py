@@ -2,7 +2,8 @@
 """Where a VecEnv.step(numpy) of the headline config (or: <envs> <task> <per_side>) spends its time on the host: the action copy into the mapped buffer, the launch
 call, the wait. (time.perf_counter_ns around the three pieces; ~0.1 us of timer overhead each.) Then VecEnv.step's own order -- header word,
 doorbell, copy under the launch, wait (ac_step_host_actions) -- timed inside the library, with the kernel's retry counter, for the
-library's share of the copy behind the doorbell or for every share of a comma-separated fourth argument."""
+library's share of the copy behind the doorbell or for every share of a comma-separated fourth argument. Last, VecEnv.step minus the
+library's timers -- the time a step spends outside the library -- through ctypes and through the native entry (csrc/native_step.cpp)."""
 import ctypes as C
 import os
 import sys
@@ -56,7 +57,11 @@ print(f"VecEnv.step: {(now() - t0) / 3000 / 1e3:.2f} us/step")
 # re-issued over the run (a path that retries in steady state is not one to ship). Fourth argument: the shares to sweep.
 fractions = [float(x) for x in sys.argv[4].split(",")] if len(sys.argv) > 4 else [pkg.capi.AC_LATE_FRACTION_DEFAULT]
 lib = env.lib
-for f in fractions:
+
+
+def late_pieces(env, f, label):
+    """2000 timed steps at share f; returns (VecEnv.step, the sum of the library's four timers) in us per step"""
+    h = env._h
     lib.check(lib.ac_late_config(h, f, -1, -1, 0), "ac_late_config")
     for it in range(300):
         env.step(acts[it & 15])
@@ -70,9 +75,35 @@ for f in fractions:
     dt = (now() - t0) / K / 1e3
     st = pkg.capi.AcLateStats()
     lib.check(lib.ac_late_stats(h, C.byref(st)), "ac_late_stats")
+    lib.check(lib.ac_late_config(h, -1.0, -1, -1, 0), "ac_late_config")
     n = max(1, st.timed_steps - before.timed_steps)
     d = lambda name: (getattr(st, name) - getattr(before, name)) / n
-    print(f"late actions f={f:.3f}: {st.steps - before.steps} late steps of {K}, retries {st.retries - before.retries} in {st.retry_steps - before.retry_steps} steps   "
+    print(f"{label} f={f:.3f}: {st.steps - before.steps} late steps of {K}, retries {st.retries - before.retries} in {st.retry_steps - before.retry_steps} steps   "
           f"copy before {d('copy_before_us'):.2f} us  dispatch {d('dispatch_us'):.2f} us  copy after (under the wait) {d('copy_after_us'):.2f} us  "
           f"wait {d('wait_us'):.2f} us   VecEnv.step {dt:.2f} us/step")
+    return dt, d("copy_before_us") + d("dispatch_us") + d("copy_after_us") + d("wait_us")
+
+
+for f in fractions:
+    late_pieces(env, f, "late actions")
 env.close()
+# VecEnv.step minus the library's own timers: what a step spends outside the library, through ctypes (AIRCOMBAT_NATIVE_STEP=0: set choice,
+# checks, address, foreign call, result objects, all in the interpreter) and through the native entry (csrc/native_step.cpp; the figure
+# still holds the result objects' construction, which now runs between the doorbell and the wait and shortens the wait by as much).
+# Two passes each, alternating, so that a drift of the machine shows as a spread and not as a difference.
+rows = {"ctypes": [], "native": []}
+for rep in range(2):
+    for path in ("ctypes", "native"):
+        os.environ["AIRCOMBAT_NATIVE_STEP"] = "0" if path == "ctypes" else "1"
+        e2 = (pkg.HipShareVecEnv if cfg.n_agents > 2 else pkg.HipVecEnv)(cfg, E, seed=1)
+        if path == "native" and e2._native is None:
+            print("outside the library, native path: the extension is not built here")
+            e2.close()
+            continue
+        e2.reset()
+        dt, inside = late_pieces(e2, fractions[-1], f"VecEnv.step through {path}")
+        rows[path].append((dt, inside))
+        e2.close()
+for path, r in rows.items():
+    if r:
+        print(f"outside the library, {path} path: " + ", ".join(f"{dt:.2f} - {inside:.2f} = {dt - inside:.2f} us" for dt, inside in r))
