@@ -25,7 +25,9 @@ _TORCH_EXPORTS = {"DeviceGRUFunction": "gru_train", "DeviceGRULayer": "gru_train
                   "DeviceMLPBlockFunction": "mlp_train", "DeviceMLPLayer": "mlp_train", "mlp_block": "mlp_train", "use_device_mlp": "mlp_train",
                   "DeviceActEvalFunction": "act_train", "act_evaluate": "act_train", "use_device_act": "act_train",
                   "DevicePPOLossFunction": "ppo_update", "ppo_loss": "ppo_update", "device_clip_adam_step": "ppo_update", "DevicePPOTrainer": "ppo_update",
-                  "DeviceDiscriminator": "mutual_support"}
+                  "DeviceDiscriminator": "mutual_support",
+                  "DeviceActorEvalFunction": "net_train", "DeviceCriticFunction": "net_train", "value_head": "net_train", "feature_norm": "net_train",
+                  "shoot_prior": "net_train", "use_device_networks": "net_train"}
 
 
 def __getattr__(name):
@@ -42,4 +44,5 @@ __all__ = ["AcConfig", "AcInitState", "Lib", "load_library", "library_path", "Hi
            "DeviceGRULayerFunction", "gru_layer", "DeviceFusedGRULayer", "use_device_gru_layer",
            "DeviceMLPBlockFunction", "DeviceMLPLayer", "mlp_block", "use_device_mlp",
            "DeviceActEvalFunction", "act_evaluate", "use_device_act",
-           "DevicePPOLossFunction", "ppo_loss", "device_clip_adam_step", "DevicePPOTrainer", "DeviceDiscriminator"]
+           "DevicePPOLossFunction", "ppo_loss", "device_clip_adam_step", "DevicePPOTrainer", "DeviceDiscriminator",
+           "DeviceActorEvalFunction", "DeviceCriticFunction", "value_head", "feature_norm", "shoot_prior", "use_device_networks"]

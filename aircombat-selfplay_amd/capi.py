@@ -151,9 +151,20 @@ class AcConfig(C.Structure):
     ]
 
 
+AC_NET_MAX_BLOCKS = 4
+AC_NET_MAX_PARAMS = 64
+
+
 class AcActHeads(C.Structure):
     """ac_act_heads_t: the training action heads' configuration (ac_act_eval_*)."""
     _fields_ = [("n_cat", C.c_int32), ("nvec", C.c_int32 * 8), ("n_shoot_cols", C.c_int32)]
+
+
+class AcNet(C.Structure):
+    """ac_net_t: one network of the policy as the chains read it (ac_actor_eval_*, ac_critic_*)."""
+    _fields_ = [("obs_dim", C.c_int32), ("feature_norm", C.c_int32), ("base_blocks", C.c_int32), ("head_blocks", C.c_int32), ("heads", AcActHeads),
+                ("mlp_products", C.c_int32), ("gru_products", C.c_int32), ("gru_dense_products", C.c_int32), ("feature_norm_eps", C.c_float),
+                ("block_eps", C.c_float * (2 * AC_NET_MAX_BLOCKS)), ("gru_eps", C.c_float), ("params", C.c_void_p * AC_NET_MAX_PARAMS)]
 
 
 class AcOptimEntry(C.Structure):
@@ -366,6 +377,20 @@ SIGNATURES = {
     "ac_optim_grad_norms": (C.c_int, [C.c_int32, _p, _p, _p, C.c_int32, C.c_int32, _p, _p]),
     "ac_optim_clip_adam_step": (C.c_int, [C.c_int32, _p, _p, _p, C.c_int32, C.c_int32, _p, C.c_double, C.c_int32]),
     "ac_ppo_update_constant": (C.c_int32, [C.c_int32]),
+    "ac_value_head_forward": (C.c_int, [C.c_int32, _p, C.c_int32, _p, _p, _p, _p]),
+    "ac_value_head_workspace_floats": (C.c_int64, [C.c_int32]),
+    "ac_value_head_backward": (C.c_int, [C.c_int32, _p, C.c_int32] + [_p] * 7),
+    "ac_feature_norm_forward": (C.c_int, [C.c_int32, _p, C.c_int32, C.c_int32, C.c_float] + [_p] * 5),
+    "ac_feature_norm_workspace_floats": (C.c_int64, [C.c_int32, C.c_int32]),
+    "ac_feature_norm_backward": (C.c_int, [C.c_int32, _p, C.c_int32, C.c_int32] + [_p] * 8),
+    "ac_shoot_prior": (C.c_int, [C.c_int32, _p, C.c_int32, C.c_int32, _p, _p, _p]),
+    "ac_net_constant": (C.c_int32, [C.c_int32]),
+    "ac_net_workspace_floats": (C.c_int64, [C.POINTER(AcNet), C.c_int32, C.c_int32]),
+    "ac_net_saved_floats": (C.c_int64, [C.POINTER(AcNet), C.c_int32, C.c_int32]),
+    "ac_actor_eval_forward": (C.c_int, [C.c_int32, _p, C.POINTER(AcNet), C.c_int32, C.c_int32] + [_p] * 8),
+    "ac_actor_eval_backward": (C.c_int, [C.c_int32, _p, C.POINTER(AcNet), C.c_int32, C.c_int32] + [_p] * 9),
+    "ac_critic_forward": (C.c_int, [C.c_int32, _p, C.POINTER(AcNet), C.c_int32, C.c_int32] + [_p] * 7),
+    "ac_critic_backward": (C.c_int, [C.c_int32, _p, C.POINTER(AcNet), C.c_int32, C.c_int32] + [_p] * 8),
     "ac_last_error": (C.c_char_p, []),
     "ac_version": (C.c_char_p, []),
     # include/aircombat_buffer.h

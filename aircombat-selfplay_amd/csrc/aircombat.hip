@@ -3048,6 +3048,7 @@ int ac_get_missile_target(ac_env_t* h, int32_t env, int32_t agent, int32_t k, in
 #include "league_collect.hpp"
 #include "gru_layer_train.hpp"
 #include "gru_layer_train_split.hpp"
+#include "net_train.hpp"
 #include "mutual_support.hpp"
 #include "math_probe.hpp"
 #include "missile_probe.hpp"

@@ -90,15 +90,18 @@ def gru_layer(x, hxs, masks, w_ih, w_hh, b_ih, b_hh, gamma, beta, eps=1e-5, prod
     return DeviceGRULayerFunction.apply(x, hxs, masks, w_ih, w_hh, b_ih, b_hh, gamma, beta, float(eps), save, code, dense)
 
 
-def check_layer(gru, norm, where="rnn"):
+def check_layer(gru, norm, where="rnn", device=True):
     """UnsupportedPolicy unless (gru, norm) is what the kernels run: whatever check_gru accepts, then nn.LayerNorm((128,)) with affine
-    parameters, float32 on a CUDA device."""
+    parameters, float32 and, with ``device``, on a CUDA device."""
     said = []   # everything wrong with the layer in one message: the GRU's part as check_gru words it, then the LayerNorm's
     try:
-        gru_train.check_gru(gru, where + ".gru")
+        if device:   # the call as it was before ``device`` existed: callers and tests that stand in for check_gru take two arguments
+            gru_train.check_gru(gru, where + ".gru")
+        else:
+            gru_train.check_gru(gru, where + ".gru", device=False)
     except UnsupportedPolicy as exc:
         said.append(str(exc))
-    bad = layernorm_faults(norm)
+    bad = layernorm_faults(norm, device)
     if bad:
         said.append(f"{where}.norm: " + ", ".join(bad))
     if said:

@@ -79,9 +79,9 @@ def gru_seq(x, hxs, masks, w_ih, w_hh, b_ih, b_hh, products="fp32"):
     return DeviceGRUFunction.apply(x, hxs, masks, w_ih, w_hh, b_ih, b_hh, save, code)
 
 
-def check_gru(gru, where="gru"):
+def check_gru(gru, where="gru", device=True):
     """UnsupportedPolicy unless ``gru`` is what the kernels run: nn.GRU 128 -> 128, one layer, with bias, not batch-first, not
-    bidirectional, float32 on a CUDA device."""
+    bidirectional, float32 and, with ``device``, on a CUDA device."""
     if not isinstance(gru, nn.GRU):
         raise UnsupportedPolicy(f"{where}: not an nn.GRU ({type(gru).__name__})")
     bad = []
@@ -100,7 +100,7 @@ def check_gru(gru, where="gru"):
     w = gru.weight_hh_l0
     if w.dtype != torch.float32:
         bad.append(f"dtype {w.dtype} (only float32)")
-    if w.device.type != "cuda":
+    if device and w.device.type != "cuda":
         bad.append(f"device {w.device} (only a CUDA device)")
     if bad:
         raise UnsupportedPolicy(f"{where}: " + ", ".join(bad))

@@ -691,6 +691,92 @@ int ac_optim_clip_adam_step(int32_t device_id, void* stream, const ac_optim_entr
  * most, 2 elements per optimiser chunk, 3 entries at most, 4 groups at most; -1 otherwise */
 int32_t ac_ppo_update_constant(int32_t which);
 
+/* ---- the PPO update's actor and critic as one call each ("The networks as one call"). First the three pieces no layer
+ * above covers, each usable on its own; then the chains. Every device pointer is float32; the calls launch on `stream` and return at
+ * once; sums over rows are fixed-order (no atomics), so results are bit-identical from run to run. Refused, each with its message and
+ * before any launch: a NULL required pointer, M < 1, K outside 1 .. 256, a row count beyond the kernels' 32-bit index, a misaligned x, w
+ * or dx of the value head (16 bytes). */
+/* the critic's value_out, nn.Linear(128, 1): d_v [M] = x w + b, x [M, 128], w [128], b [1] */
+int ac_value_head_forward(int32_t device_id, void* stream, int32_t M, const float* d_x, const float* d_w, const float* d_b, float* d_v);
+/* floats of ac_value_head_backward's d_workspace: 129 per workgroup, one workgroup per 64-row tile up to 256; -1: refused */
+int64_t ac_value_head_workspace_floats(int32_t M);
+/* two launches: upstream d_g [M] -> d_dx [M, 128] = g w (NULL: not computed), d_dw [128] = sum_m g[m] x[m], d_db [1] = sum_m g[m] */
+int ac_value_head_backward(int32_t device_id, void* stream, int32_t M, const float* d_g, const float* d_x, const float* d_w, float* d_workspace,
+                           float* d_dx, float* d_dw, float* d_db);
+/* base.feature_norm, nn.LayerNorm(K) over the raw observation: d_y [M, K] = (x - mean) / sqrt(var + eps) * gamma + beta, biased
+ * variance; d_stats [M, 2] (each row's mean and 1 / sqrt(var + eps)) for a backward, or NULL */
+int ac_feature_norm_forward(int32_t device_id, void* stream, int32_t M, int32_t K, float eps, const float* d_x, const float* d_gamma,
+                            const float* d_beta, float* d_y, float* d_stats);
+/* floats of ac_feature_norm_backward's d_workspace: 2 K per workgroup, one workgroup per 64-row tile up to 256; -1: refused */
+int64_t ac_feature_norm_workspace_floats(int32_t M, int32_t K);
+/* two launches: upstream d_dy [M, K], the forward's d_x and d_stats -> d_dx [M, K] (NULL: not computed; the observation never needs
+ * it), d_dgamma, d_dbeta [K] */
+int ac_feature_norm_backward(int32_t device_id, void* stream, int32_t M, int32_t K, const float* d_dy, const float* d_x, const float* d_gamma,
+                             const float* d_stats, float* d_workspace, float* d_dx, float* d_dgamma, float* d_dbeta);
+/* the reference actor's shoot prior (algorithms/ppo/ppo_actor.py:40-49) from d_obs [M, K], K >= 14, in fp32: with a = obs[11] *
+ * 57.29577951308232f and d = obs[13] * 10000.0f, alpha0 = 10 if d <= 8000, else 6 if d <= 12000, else 3; beta0 = 3 if a <= 22.5, else
+ * 6 if a <= 45, else 10 (a NaN keeps 3 and 10). -> d_alpha0, d_beta0 [M] */
+int ac_shoot_prior(int32_t device_id, void* stream, int32_t M, int32_t K, const float* d_obs, float* d_alpha0, float* d_beta0);
+/* the three kernels' constants: 0 rows per tile, 1 the forwards' workgroups at most, 2 the backwards' (also their partial sets at
+ * most); -1 otherwise */
+int32_t ac_net_constant(int32_t which);
+
+/* One network of the reference's PPO / MAPPO policy: [feature_norm] -> base.mlp's blocks -> the GRU layer -> the head MLP's blocks
+ * (act.mlp of the actor, mlp of the critic) -> the action heads (actor) or value_out (critic). heads.n_cat == 0 says critic.
+ * `params` holds device pointers in this order, `count` of them:
+ *   feature_norm (if present): gamma, beta [obs_dim]
+ *   each base block:           W [128, K], b, gamma, beta [128]      (K = obs_dim for the first, 128 after)
+ *   the GRU layer:             W_ih, W_hh [384, 128], b_ih, b_hh [384], the LayerNorm's gamma, beta [128]
+ *   each head block:           W [128, 128], b, gamma, beta [128]
+ *   actor:  each categorical head's W [nvec[h], 128], b [nvec[h]], then with shoot columns the one shoot head's W [2, 128], b [2]
+ *   critic: value_out's W [128], b [1]
+ * A backward's d_grads is a HOST array of `count` device pointers in the same order; every one is written, nothing is accumulated. */
+#define AC_NET_MAX_BLOCKS 4
+#define AC_NET_MAX_PARAMS 64
+typedef struct {
+  int32_t obs_dim;               /* the observation's width, 1 .. 256 */
+  int32_t feature_norm;          /* 1: base.feature_norm is present */
+  int32_t base_blocks;           /* blocks of base.mlp, 1 .. 4 */
+  int32_t head_blocks;           /* blocks of the head MLP, 0 .. 4 */
+  ac_act_heads_t heads;          /* the actor's heads; n_cat == 0: a critic */
+  int32_t mlp_products;          /* AC_PRODUCTS_ of the MLP blocks, */
+  int32_t gru_products;          /* of the GRU's recurrence and */
+  int32_t gru_dense_products;    /* of the GRU layer's dense products */
+  float feature_norm_eps;
+  float block_eps[2 * AC_NET_MAX_BLOCKS];   /* the blocks' LayerNorm eps: base blocks first, then head blocks */
+  float gru_eps;                 /* the GRU layer's LayerNorm eps */
+  const float* params[AC_NET_MAX_PARAMS];
+} ac_net_t;
+/* Both sizes below round every segment up to a multiple of 4 floats (r4), with M = N T, B = base_blocks + head_blocks:
+ * d_saved = [feature_norm: r4(2 M) + r4(M obs_dim)] + B r4(2 M) + (B + 1) 128 M  (each stage's output: an input of the next)
+ *           + 128 M (the GRU's y) + 512 M (its gates) + r4(2 M) (its stats) + [shoot columns: 2 r4(M)].
+ * It holds what the layer calls keep one by one: each block's input and stats and the GRU layer's y, saved and stats.
+ * d_workspace = the larger of
+ *   forward:  384 M + 128 N + d_saved's floats without the r4(2 M) terms and the 512 M (the activations of a forward that saves nothing)
+ *   backward: 2 * 128 M + [feature_norm: r4(M obs_dim)] + the largest workspace of the layers' own backwards for this shape.
+ * -1 with ac_last_error: a NULL net, N or T < 1, obs_dim outside 1 .. 256, base_blocks outside 1 .. 4, head_blocks outside 0 .. 4,
+ * an unknown products code, heads that ac_act_eval_* refuses, shoot columns with obs_dim < 14 or without categorical heads. */
+int64_t ac_net_workspace_floats(const ac_net_t* net, int32_t N, int32_t T);
+int64_t ac_net_saved_floats(const ac_net_t* net, int32_t N, int32_t T);
+/* The actor's evaluate_actions: the prior (with shoot columns), [feature_norm], the base blocks, the GRU layer, the head blocks and the
+ * heads, queued back to back by the calls above (ac_shoot_prior, ac_feature_norm_*, ac_mlp_block_*_p, ac_gru_layer_*_pd, ac_act_eval_*).
+ * d_obs [N T, obs_dim] step-major, d_hxs [N, 128], d_masks [N T], d_actions [N T, n_cat + n_shoot_cols] -> d_logp, d_ent [N T], unscaled.
+ * d_saved NULL: nothing is kept for a backward. d_workspace and d_saved are caller-owned, 16-byte aligned; nothing is allocated,
+ * nothing waits for the device. Refused as the sizes above, and: a NULL pointer (a parameter's too), a description of the other kind. */
+int ac_actor_eval_forward(int32_t device_id, void* stream, const ac_net_t* net, int32_t N, int32_t T, const float* d_obs, const float* d_hxs,
+                          const float* d_masks, const float* d_actions, float* d_workspace, float* d_saved, float* d_logp, float* d_ent);
+/* upstream d_dlogp, d_dent [N T] (NULL: zero) and the forward's inputs and d_saved -> every parameter's gradient in d_grads */
+int ac_actor_eval_backward(int32_t device_id, void* stream, const ac_net_t* net, int32_t N, int32_t T, const float* d_dlogp, const float* d_dent,
+                           const float* d_obs, const float* d_hxs, const float* d_masks, const float* d_actions, const float* d_saved,
+                           float* d_workspace, float* const* d_grads);
+/* The critic: [feature_norm], the base blocks, the GRU layer, the head blocks and value_out -> d_values [N T], d_h_T [N, 128] */
+int ac_critic_forward(int32_t device_id, void* stream, const ac_net_t* net, int32_t N, int32_t T, const float* d_obs, const float* d_hxs,
+                      const float* d_masks, float* d_workspace, float* d_saved, float* d_values, float* d_h_T);
+/* upstream d_dvalues [N T] and d_dh_T [N, 128] (NULL: zero) -> every parameter's gradient in d_grads */
+int ac_critic_backward(int32_t device_id, void* stream, const ac_net_t* net, int32_t N, int32_t T, const float* d_dvalues, const float* d_dh_T,
+                       const float* d_obs, const float* d_hxs, const float* d_masks, const float* d_saved, float* d_workspace,
+                       float* const* d_grads);
+
 const char* ac_last_error(void);
 const char* ac_version(void);
 
